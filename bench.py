@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark: utterances/sec of PESQ-wb + STOI/ESTOI on 10 s @ 16 kHz pairs (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--length L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--length L] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +13,7 @@ One step = the drop-in call ``PESQ_STOI(16000, use_gpu=True)(clean, noisy)`` on 
 The call runs the fused joint entry fsem_pesq_stoi_f32 (one read of the inputs; scores bitwise
 equal to the two separate API calls; ``--separate`` runs ``PESQ(...)`` + ``STOI(...)`` instead).
 With N > 1 ranks every rank also all-gathers the job's [B, 3] scores over RCCL (xGMI).
-``scores_path`` reports the engine API alone (``PESQ_STOI.scores`` + one device->host copy).
+``scores_path`` (with ``--full``) reports the engine API alone (``PESQ_STOI.scores`` + one device->host copy).
 Weak scaling: every rank owns its own shard of utterances, generated in HBM before timing.
 
 ``--gpus N`` without a torch.distributed launcher starts the N ranks itself (a child
@@ -22,10 +23,17 @@ device count is an error.  This one-process-per-GPU form is what the driver's sc
 devices through ``PESQ_STOI(..., devices=N)`` (multidevice.py) on a batch held by device 0, the
 shards' peer copies included.
 
-Rank 0 prints ONE JSON line with the metric, the roofline of the dominant kernel
-(pesq_front<joint>: algorithmic bytes / its HIP-event-timed duration vs 8 TB/s), the CPU
-baseline (the package's use_gpu=False path on the host's cores at batch 4 and 64, as
+Rank 0 prints ONE JSON line with the metric and the step-level roofline that follows from
+``ms_per_step``.  A plain run does only that: set up, warm up, time the steps, print.  ``--full``
+adds the legs that take runs of their own: the roofline of the dominant kernel
+(pesq_front<joint>: algorithmic bytes / its HIP-event-timed duration vs 8 TB/s), ``scores_path``,
+the CPU baseline (the package's use_gpu=False path on the host's cores at batch 4 and 64, as
 SURVEY.md 8(d) / BASELINE.md ask) and the oracle CPU restatement beside it (``cpu_oracle``).
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller, on rank 0, as
+``DIR/<name>.npy`` (float64): PESQ, STOI, ESTOI, one value per utterance of the rank's batch in
+row order (the workloads that score one metric write that one).  The inputs are seeded, so two
+builds run with the same arguments score the same signals.
 """
 from __future__ import annotations
 
@@ -55,10 +63,15 @@ def parse():
                          "(workspace allocation, clocks)")
     ap.add_argument("--batch", type=int, default=4096, help="utterance pairs per GPU")
     ap.add_argument("--length", type=int, default=160000, help="samples per utterance (16 kHz)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="oracle CPU leg time budget")
-    ap.add_argument("--cpu-calls", type=int, default=7, help="CPU-baseline calls per batch size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernel-reps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the dominant kernel's roofline, the "
+                         "scores path, the CPU baseline and the oracle CPU leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the scores the last timed step returned as DIR/<name>.npy (float64, rank 0)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: oracle CPU leg time budget")
+    ap.add_argument("--cpu-calls", type=int, default=7, help="with --full: CPU-baseline calls per batch size")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the two CPU legs out")
+    ap.add_argument("--kernel-reps", type=int, default=5, help="with --full: timed launches of the dominant kernel")
     ap.add_argument("--separate", action="store_true", help="two API calls (PESQ, STOI) instead of the joint entry")
     ap.add_argument("--device-list", default=None,
                     help="with --single-process: explicit device indices, e.g. 0,0 (repeats allowed: "
@@ -311,6 +324,8 @@ def pmc_kernel(summary: dict, kernel) -> dict:
 
 
 def _timed(step, args, dev, distributed):
+    """(seconds of the args.steps timed steps, what the last of them returned)."""
+    last = None
     for _ in range(args.warmup):
         step()
     if distributed:
@@ -318,7 +333,7 @@ def _timed(step, args, dev, distributed):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     if distributed:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -327,7 +342,24 @@ def _timed(step, args, dev, distributed):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return dt
+    return dt, last
+
+
+def dump_outputs(directory, last, names=("PESQ", "STOI", "ESTOI")):
+    """--dump-outputs: `last` is what the last timed step returned -- the drop-in call's list of
+    dicts, or a [B] / [B, len(names)] host tensor of scores -- written as directory/<name>.npy,
+    float64, one value per row."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    if isinstance(last, list):
+        cols = {k: np.array([d[k] for d in last], dtype=np.float64) for k in names}
+    else:
+        a = last.detach().cpu().numpy().astype(np.float64)
+        a = a.reshape(a.shape[0], -1)
+        assert a.shape[1] == len(names), (a.shape, names)
+        cols = {k: np.ascontiguousarray(a[:, i]) for i, k in enumerate(names)}
+    for k, v in cols.items():
+        np.save(os.path.join(directory, f"{k}.npy"), v)
 
 
 def run_c3(args, world, rank, dev, distributed):
@@ -349,7 +381,9 @@ def run_c3(args, world, rank, dev, distributed):
         local = torch.stack([s, e], 1)
         return local.cpu() if rank == 0 else None
 
-    dt = _timed(step, args, dev, distributed)
+    dt, last = _timed(step, args, dev, distributed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, ("STOI", "ESTOI"))
     if rank == 0:
         print(json.dumps({
             "metric": "utterances/sec STOI+ESTOI, 5s@16kHz, batch 8192 (config 3)",
@@ -387,7 +421,9 @@ def run_pesq(args, world, rank, dev, distributed):
         p = pesq.scores(clean, noisy)
         return p.cpu() if rank == 0 else None
 
-    dt = _timed(step, args, dev, distributed)
+    dt, last = _timed(step, args, dev, distributed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, ("PESQ",))
     if aligned:
         found = int((pesq.last_delays.long() == delay).sum())
     if rank == 0:
@@ -450,7 +486,9 @@ def run_c5(args, world, rank, dev, distributed):
         res = torch.cat([out8, out16])
         return res.cpu() if rank == 0 else None
 
-    dt = _timed(step, args, dev, distributed)
+    dt, last = _timed(step, args, dev, distributed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     if rank == 0:
         audio_s = float(secs.sum())
         print(json.dumps({
@@ -511,7 +549,9 @@ def run_single_process(args):
     def step():
         return metric(clean, noisy)
 
-    dt = _timed(step, args, dev, False)
+    dt, last = _timed(step, args, dev, False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     print(json.dumps({
         "metric": METRIC + " (one process, devices=N)", "value": round(B * args.steps / dt, 2),
         "unit": "utterances/s", "n_gpus": len(set(devices)), "devices": devices, "steps": args.steps,
@@ -600,18 +640,24 @@ def main():
         full = gather_scores(local, world * B) if distributed else local
         return full.cpu() if rank == 0 else None
 
-    # the dominant kernel's roofline (HIP-event timed launches of its stage entry) first: the
-    # GPU's clocks are still ramping during the first steps after the input generation
-    roof = kernel_roofline(clean[:launch_rows], noisy[:launch_rows], args.kernel_reps, joint=not args.separate,
-                           config_batch=B)
-    dt = _timed(step, args, dev, distributed)
+    # --full: the dominant kernel's roofline (HIP-event timed launches of its stage entry) first:
+    # the GPU's clocks are still ramping during the first steps after the input generation
+    roof = {}
+    if args.full:
+        roof = kernel_roofline(clean[:launch_rows], noisy[:launch_rows], args.kernel_reps, joint=not args.separate,
+                               config_batch=B)
+    dt, last = _timed(step, args, dev, distributed)
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
-    dt_s = _timed(scores_step, args, dev, distributed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    del last
+    if args.full:
+        dt_s, _ = _timed(scores_step, args, dev, distributed)
 
     if rank == 0:
         cpu = oracle = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(clean, noisy, batches=tuple(sorted({min(4, B), min(64, B)})), calls=args.cpu_calls)
             oracle = cpu_oracle(clean, noisy, args.cpu_seconds)
         out = {
@@ -625,11 +671,14 @@ def main():
                                        "the inputs)") + " -> list of dicts"),
                        "batch_per_gpu": B, "global_batch": world * B, "length": L, "sample_rate": 16000,
                        "parallelism": f"dp{world} (utterance shards, RCCL all-gather of scores)"},
-            "roofline": {**roof, "step": step_roofline(B, L, ms_per_step)}, "cpu_baseline": cpu, "cpu_oracle": oracle,
-            "scores_path": {"value": round(world * B * args.steps / dt_s, 2), "unit": "utterances/s",
-                            "ms_per_step": round(dt_s / args.steps * 1e3, 3),
-                            "what": "PESQ_STOI.scores + one device->host copy (no list of dicts)"},
+            "roofline": {**roof, "step": step_roofline(B, L, ms_per_step)},
         }
+        if args.full:
+            out.update({
+                "cpu_baseline": cpu, "cpu_oracle": oracle,
+                "scores_path": {"value": round(world * B * args.steps / dt_s, 2), "unit": "utterances/s",
+                                "ms_per_step": round(dt_s / args.steps * 1e3, 3),
+                                "what": "PESQ_STOI.scores + one device->host copy (no list of dicts)"}})
         print(json.dumps(out), flush=True)
     if distributed:
         dist.barrier()

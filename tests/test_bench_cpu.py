@@ -23,6 +23,30 @@ def test_defaults_are_the_headline_config(monkeypatch):
     a = bench.parse()
     assert (a.gpus, a.batch, a.length, a.workload) == (1, 4096, 160000, "c2")
     assert a.steps > 0 and a.warmup >= 0 and not a.separate
+    assert a.full is False and a.dump_outputs is None  # a plain run: the headline figure alone
+
+
+def test_full_and_dump_outputs_options(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--full",
+                                      "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "somewhere" and (a.steps, a.warmup) == (7, 2)
+
+
+def test_dump_outputs_writes_one_float64_array_per_score(tmp_path):
+    """The drop-in call's list of dicts and the scores-path tensors both land as <name>.npy."""
+    rows = [{"PESQ": 1.5, "STOI": 0.25, "ESTOI": 0.125}, {"PESQ": 4.0, "STOI": 0.5, "ESTOI": float("nan")}]
+    bench.dump_outputs(str(tmp_path / "a"), rows)
+    for k in ("PESQ", "STOI", "ESTOI"):
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float64 and got.shape == (2,)
+        assert np.array_equal(got, np.array([r[k] for r in rows]), equal_nan=True)
+    bench.dump_outputs(str(tmp_path / "b"), torch.tensor([[0.5, 0.25], [0.75, 0.125]]), ("STOI", "ESTOI"))
+    assert np.array_equal(np.load(tmp_path / "b" / "ESTOI.npy"), np.array([0.25, 0.125]))
+    bench.dump_outputs(str(tmp_path / "c"), torch.tensor([1.0, 2.0, 3.0]), ("PESQ",))
+    got = np.load(tmp_path / "c" / "PESQ.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, np.array([1.0, 2.0, 3.0]))
+    assert sorted(os.listdir(tmp_path / "c")) == ["PESQ.npy"]
 
 
 def test_cpu_oracle_fields():

@@ -1,6 +1,6 @@
 """bench.py end to end on the GPU at a small size (the driver's contract: one JSON line on stdout
-with the metric, throughput, roofline of the dominant kernel and the CPU legs), run as a child
-process like the driver runs it."""
+with the metric and throughput; with --full also the roofline of the dominant kernel and the CPU
+legs), run as a child process like the driver runs it."""
 import json
 import os
 import subprocess
@@ -13,9 +13,9 @@ REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
 def test_bench_json_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--batch", "64", "--length", "48000",
-                          "--steps", "2", "--warmup", "1", "--kernel-reps", "2", "--cpu-seconds", "0.5",
-                          "--cpu-calls", "2"],
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--batch", "64",
+                          "--length", "48000", "--steps", "2", "--warmup", "1", "--kernel-reps", "2",
+                          "--cpu-seconds", "0.5", "--cpu-calls", "2"],
                          cwd=REPO, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -42,6 +42,39 @@ def test_bench_json_line_contract():
     assert d["scores_path"]["value"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline figure alone (no kernel roofline, CPU legs or
+    scores path), and --dump-outputs writes what the last timed step returned: the drop-in call's
+    scores of the seeded batch, equal to the same call made here."""
+    import numpy as np
+    import torch
+    from fast_speech_enhancement_metrics_amd import PESQ_STOI
+    from fast_speech_enhancement_metrics_amd.synthetic import speech_like_pairs
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--batch", "64",
+                          "--length", "48000", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)],
+                         cwd=REPO, capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    with open(os.path.join(REPO, "BASELINE.json")) as f:
+        assert d["metric"] == json.load(f)["metric"]
+    assert d["unit"] == "utterances/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["value"] > 0 and abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    for key in ("cpu_baseline", "cpu_oracle", "scores_path"):
+        assert key not in d, key
+    assert set(d["roofline"]) == {"step"} and d["roofline"]["step"]["ms_per_step"] > 0
+    assert sorted(os.listdir(dump)) == ["ESTOI.npy", "PESQ.npy", "STOI.npy"]
+    clean, noisy, _ = speech_like_pairs(64, 48000, 16000, seed=42, device=torch.device("cuda", 0))
+    want = PESQ_STOI(16000, use_gpu=True)(clean, noisy)
+    for k in ("PESQ", "STOI", "ESTOI"):
+        a = np.load(dump / f"{k}.npy")
+        assert a.dtype == np.float64 and a.shape == (64,) and np.isfinite(a).all()
+        assert np.array_equal(a, np.array([r[k] for r in want], dtype=np.float64)), k
+
+
 def test_bench_gpus_beyond_visible_fails():
     """--gpus N without a launcher on a box with fewer devices: a clear error, not a 1-GPU run."""
     import torch
@@ -64,7 +97,7 @@ def test_bench_rccl_path_one_rank_pipelined():
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                               "--master-addr", "127.0.0.1", "--master-port", str(port),
                               os.path.join(REPO, "bench.py"), "--gpus", "1", "--batch", "4096", "--length", "16000",
-                              "--steps", "2", "--warmup", "1", "--kernel-reps", "1", "--no-cpu-baseline"],
+                              "--steps", "2", "--warmup", "1", "--full", "--kernel-reps", "1", "--no-cpu-baseline"],
                              cwd=REPO, capture_output=True, text=True, timeout=240, env=env)
         if "EADDRINUSE" not in out.stderr:
             break
