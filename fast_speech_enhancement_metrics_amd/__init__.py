@@ -4,6 +4,7 @@
     PESQ(sample_rate=16000, use_gpu=True)(clean, denoised)  -> [{"PESQ": ...}, ...]
     STOI(sample_rate=16000, use_gpu=True)(clean, denoised)  -> [{"STOI": ..., "ESTOI": ...}, ...]
     PESQ_STOI(16000, use_gpu=True)(clean, denoised)        -> [{"PESQ", "STOI", "ESTOI"}, ...]  (one pass)
+    SDR(sample_rate=16000, use_gpu=True)(clean, denoised)   -> [{"SI-SDR", "SNR", "SegSNR"}, ...]  (extension)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
 """
@@ -11,6 +12,7 @@ from .base import BaseMetric
 from .PESQ import PESQ
 from .STOI import STOI
 from .joint import PESQ_STOI
+from .SDR import SDR
 from .alignment import time_align
 
-__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "time_align"]
+__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "time_align"]

@@ -663,3 +663,42 @@ def pesq_p862(clean: torch.Tensor, noisy: torch.Tensor, lengths=None, max_delay:
         if iv:
             bad[b, :len(iv)] = torch.tensor(iv, dtype=torch.int32)
     return mos, ds, nb, bad
+
+
+# ----------------------------------------------------------------------------- SDR family
+# SI-SDR, SNR and segmental SNR (not in the reference; engine: csrc/sdr.hip, definitions:
+# include/fsem.h "SDR"), float64.
+def sdr_geometry(sample_rate: int):
+    """(hop, win) of the segmental SNR at ``sample_rate``: 7.5 ms hop, 30 ms window."""
+    hop = int(sample_rate) * 30 // 4000
+    return hop, 4 * hop
+
+
+def sdr(clean: torch.Tensor, noisy: torch.Tensor, sample_rate: int = 16000, zero_mean: bool = False):
+    """[B, n] rows at ``sample_rate`` -> (si_sdr [B], snr [B], seg_snr [B]) float64, in dB."""
+    B, n = clean.shape
+    nan = torch.full((B,), float("nan"), dtype=torch.float64)
+    if n == 0:
+        return nan, nan.clone(), nan.clone()
+    s = clean.to(torch.float64)
+    h = noisy.to(torch.float64)
+    d = h - s
+    dd = d.square().sum(1)
+    snr = 10 * torch.log10(s.square().sum(1) / dd)
+    s0, h0 = (s - s.mean(1, keepdim=True), h - h.mean(1, keepdim=True)) if zero_mean else (s, h)
+    ss, sh, hh = s0.square().sum(1), (s0 * h0).sum(1), h0.square().sum(1)
+    tt = sh / ss * sh
+    si = 10 * torch.log10(tt / (hh - tt).clamp_min(0))
+    si = torch.where(dd == 0, torch.full_like(si, float("inf")), si)
+    si = torch.where((ss == 0) | (hh == 0), nan, si)
+    hop, win = sdr_geometry(sample_rate)
+    if n >= win:
+        t = torch.arange(1, win + 1, dtype=torch.float64)
+        w = 0.5 * (1 - torch.cos(2 * math.pi * t / (win + 1)))
+        es = (s.unfold(1, win, hop) * w).square().sum(2)
+        ed = (d.unfold(1, win, hop) * w).square().sum(2)
+        seg = (10 * torch.log10(es / (ed + 1e-10) + 1e-10)).clamp(-10, 35).mean(1)
+    else:
+        seg = nan.clone()
+    bad = ~(torch.isfinite(s).all(1) & torch.isfinite(h).all(1))
+    return tuple(torch.where(bad, nan, v) for v in (si, snr, seg))

@@ -73,6 +73,12 @@ SIGNATURES = {
     "fsem_pesq_pool_f32": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp]),
     "fsem_pesq_wb_frames_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_sz,
                                                _vp]),
+    "fsem_sdr_hop": (_c_i64, [_c_i32]),
+    "fsem_sdr_frames": (_c_i64, [_c_i64, _c_i32]),
+    "fsem_sdr_chunk": (_c_i64, [_c_i32]),
+    "fsem_sdr_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32]),
+    "fsem_sdr_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
+                                     _c_sz, _vp]),
 }
 ALIGN_MAX_SEGMENTS = 32  # include/fsem.h FSEM_ALIGN_MAX_SEGMENTS
 PESQ_MAX_BAD = 16  # include/fsem.h FSEM_PESQ_MAX_BAD

@@ -63,7 +63,7 @@ extern "C" {
 #define FSEM_ERATE -5         /* unsupported sample-rate pair (see resampling)      */
 
 const char *fsem_strerror(int code);
-int fsem_version(void);  /* 10: + fsem_pesq_wb_frames_f32; 9: + fsem_pesq_bad_intervals_*, fsem_pesq_pool_f32; 8: + fsem_time_align_p862_*; 7: + fsem_host_buffer_mapped; 6: + fsem_build_id; 5: + fsem_time_align_utt_*; 4: + fsem_pre_emphasize_f32; 3: time alignment, distances */
+int fsem_version(void);  /* 11: + fsem_sdr_*; 10: + fsem_pesq_wb_frames_f32; 9: + fsem_pesq_bad_intervals_*, fsem_pesq_pool_f32; 8: + fsem_time_align_p862_*; 7: + fsem_host_buffer_mapped; 6: + fsem_build_id; 5: + fsem_time_align_utt_*; 4: + fsem_pre_emphasize_f32; 3: time alignment, distances */
 /* Content hash (16 hex digits) of the sources, headers and compile flags this library was built
  * from (fast_speech_enhancement_metrics_amd/_build.py source_hash); the host layer refuses a
  * library whose id differs from its own tree's.  "unknown" for builds outside _build.py. */
@@ -314,6 +314,43 @@ int fsem_pesq_bad_intervals_f32(const float *ref, const float *deg, const float 
 int fsem_pesq_pool_f32(const float *frames, const float *frames2, const float *dist, int64_t batch,
                        int64_t length, const int32_t *lengths, const int32_t *n_bad, const int32_t *bad,
                        float *mos, void *stream);
+
+/* ---------------------------------------------------------------- SDR: SI-SDR, SNR, segmental SNR
+ * (ABI 11) Replaces nothing in the reference, which has no energy-ratio metric.  Three numbers in
+ * dB per row pair, from ONE read of the inputs, at the rows' own `sample_rate` (no resampling);
+ * s = the clean row's first n samples, s^ = the denoised row's, d = s^ - s, n = the row's length:
+ *   snr     : 10 log10(sum s^2 / sum d^2)
+ *   si_sdr  : 10 log10(T / N), T = (sum s s^)^2 / sum s^2, N = max(sum s^^2 - T, 0) (Le Roux et al.
+ *             2019); zero_mean != 0 removes each row's own mean over its n samples first (SI-SDR
+ *             only).  NaN when sum s^2 == 0 or sum s^^2 == 0; +inf when s^ == s sample for sample
+ *             (snr too); -inf when sum s s^ == 0 with sum s^^2 > 0.  The sums are accumulated in
+ *             double: accurate while the true value lies within +-100 dB; beyond, the sign and "at
+ *             least 100 dB in magnitude, or +-inf" hold.
+ *   seg_snr : Hu & Loizou's segmental SNR.  hop = sample_rate * 30 / 4000 samples (integer division:
+ *             120 at 16 kHz, 165 at 22.05 kHz), win = 4 hop, w[t] = 0.5 (1 - cos(2 pi (t + 1) /
+ *             (win + 1))), t < win; the F = (n - win) / hop + 1 complete frames (0 when n < win);
+ *             per frame v = clamp(10 log10(sum (w s)^2 / (sum (w d)^2 + 1e-10) + 1e-10), -10, 35);
+ *             the mean of v over the frames, NaN when F == 0.  The 1e-10 terms make it scale
+ *             dependent by definition: the documented domain is float rows up to int16 range
+ *             (|x| <= 32768).  float32 sums per window quarter.
+ * A row holding a non-finite sample gives NaN in all three (other rows are unaffected), and so does
+ * a row of length 0.  There is no FSEM_ESHORT: short rows are NaN in seg_snr only.
+ *   ref, deg : [batch, length] float32 (row stride ld); rows readable up to ceil4(length) floats;
+ *              16-byte loads when both base pointers are 16-byte aligned and ld % 4 == 0, else
+ *              4-byte loads (same scores)
+ *   lengths  : NULL or [batch] int32 per-row lengths (Conventions)
+ *   si_sdr, snr, seg_snr : [batch] float32 outputs
+ * A row's scores are bitwise the same whatever the batch size, the row's position, `length` and the
+ * stream (no atomics; every sum has one order, fixed by sample_rate).
+ * sample_rate 4000 ... 192000 Hz; others give FSEM_ERATE and the queries return 0.
+ */
+int64_t fsem_sdr_hop(int32_t sample_rate);                     /* 0 when unsupported */
+int64_t fsem_sdr_frames(int64_t length, int32_t sample_rate);  /* F above */
+int64_t fsem_sdr_chunk(int32_t sample_rate);  /* samples per launch chunk: k * hop, from sample_rate only */
+size_t fsem_sdr_workspace_bytes(int64_t batch, int64_t length, int32_t sample_rate);
+int fsem_sdr_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                 const int32_t *lengths, int32_t sample_rate, int32_t zero_mean, float *si_sdr, float *snr,
+                 float *seg_snr, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }
