@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libfsem.so")
 STAMP_LIB = os.path.join(LIBDIR, "libfsem_stamps.so")  # diagnostic build (tools/stamps.py)
-SOURCES = ["pesq.hip", "pesq_back.hip", "stoi.hip", "resample.hip", "align.hip", "sdr.hip"]
+SOURCES = ["pesq.hip", "pesq_back.hip", "stoi.hip", "resample.hip", "align.hip", "sdr.hip", "runtime.hip"]
 # per-source code-generation flags: the STOI kernels and the resamplers are scheduled for ILP
 # (gfx950's max-ilp machine scheduler: joint call 7.167 vs 7.198 ms, profiles/r4_sc/; config 5
 # 224.0k vs 221.3k utt/s, profiles/r4_fl/; bitwise equal); the PESQ front end keeps the

@@ -7,8 +7,10 @@
 //      (P.862 apply_VAD), log envelope above it;
 //   2. ta_crude: the envelope lag (|j| <= M frames) of the largest plain cross-correlation
 //      (P.862 crude_align);
-//   3. ta_fine_partial + ta_fine_pick: within +-383 samples of the crude delay, the lag of the
-//      largest cross-correlation of the signals' first differences, over the whole row;
+//   3. ta_fine_fft + ta_fine_pick: within +-383 samples of the crude delay, the lag of the
+//      largest cross-correlation of the signals' first differences, over the whole row (the
+//      partials per 5120-sample chunk by fast correlation; ta_fine_partial, the direct form, is
+//      kept for A/B behind FSEM_FINE_FFT=0, see launch_fine);
 //   4. ta_shift: the aligned degraded row a[n] = deg[n + D] (0 <= n + D < L_row), else 0.
 // Delay D > 0: the degraded row lags the clean one, deg[n] ~ ref[n - D].
 // Utterance mode (fsem_time_align_utt_f32, P.862 sections 10.3-10.5 as restated in the oracle):
@@ -17,8 +19,8 @@
 //      the regions' 5120-sample pieces;
 //   6. ta_crude_utt: each utterance's envelope lag over its search window (+-300 ms around it),
 //      within +-75 frames of the row's crude lag;
-//   7. ta_fine_partial (utterance pieces): the first-difference correlation per piece around the
-//      utterance's crude delay;
+//   7. ta_fine_fft (utterance pieces; launch_fine as in stage 3): the first-difference
+//      correlation per piece around the utterance's crude delay;
 //   8. ta_pick_utt: each region's fine delay, or two delays when splitting it at a piece boundary
 //      raises the summed correlation peak by 20 % and the halves' delays differ by >= 16 samples;
 //      ta_segments: the row's segments (equal neighbours merged) and its longest segment's delay;
@@ -35,8 +37,9 @@
 //      half once more (P.862 utterance_split, two levels: up to 4 segments per utterance);
 //      ta_segments_p862: the row's segments as in stage 8, at most MAXSEG.
 // Cost was set by stage 3: 767 lags x L multiply-adds per row (about 123 M for 10 s) as
-// register-blocked packed FMAs out of LDS (ta_fine_partial); ta_fine_fft computes the same
-// partials by fast correlation (per 1280-sample block, 2048-point transforms: ~12x less work).
+// register-blocked packed FMAs out of LDS in the direct form (ta_fine_partial); the default
+// ta_fine_fft computes the same partials by fast correlation (per 1280-sample block, 2048-point
+// transforms: ~12x less work).
 // The other stages are O(L) or O(M * L / 64).
 #include "fsem_common.h"
 #include "fsem_fft.h"
@@ -66,12 +69,6 @@ constexpr int MAXSEG = 2 * MAXU;     // segments per row (include/fsem.h FSEM_AL
 constexpr int SPLIT_MIN = 16;        // samples: least delay difference of a split
 constexpr double SPLIT_GAIN = 1.2;   // least gain of the summed correlation peaks of a split
 
-__device__ __forceinline__ int64_t row_len(const int32_t *lengths, int64_t b, int64_t L) {
-  if (!lengths) return L;
-  const int64_t n = lengths[b];
-  return n < 0 ? 0 : (n > L ? L : n);
-}
-
 // LDS index of the degraded window's element m: a one-float skew every 32 so the 24 lag groups
 // of a wave (32 floats apart) read distinct banks.
 __device__ __forceinline__ int skew(int m) { return m + (m >> 5); }
@@ -82,10 +79,10 @@ __global__ void __launch_bounds__(256) ta_energy(const float *__restrict__ ref, 
                                                  int64_t B, int64_t L, int64_t ld,
                                                  const int32_t *__restrict__ lengths, float *__restrict__ E,
                                                  int64_t nfr_cap) {
-  const int64_t s = blockIdx.y + (int64_t)blockIdx.z * 65535;  // signal: 0..B-1 ref, B..2B-1 deg
+  const int64_t s = grid_row_yz();  // signal: 0..B-1 ref, B..2B-1 deg
   if (s >= 2 * B) return;
   const int64_t b = s < B ? s : s - B;
-  const int64_t nfr = row_len(lengths, b, L) / FRAME;
+  const int64_t nfr = row_length(lengths, b, L) / FRAME;
   const int64_t k = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   if (k >= nfr_cap) return;
   const int q = threadIdx.x & 15;
@@ -106,10 +103,10 @@ __global__ void __launch_bounds__(256) ta_energy(const float *__restrict__ ref, 
 __global__ void __launch_bounds__(256) ta_envelope(int64_t B, int64_t L, const int32_t *__restrict__ lengths,
                                                    float *__restrict__ E, int64_t nfr_cap) {
   __shared__ double red[8];
-  const int64_t s = blockIdx.x + (int64_t)blockIdx.y * 65535;
+  const int64_t s = grid_row_xy();
   if (s >= 2 * B) return;
   const int64_t b = s < B ? s : s - B;
-  const int64_t nfr = row_len(lengths, b, L) / FRAME;
+  const int64_t nfr = row_length(lengths, b, L) / FRAME;
   float *__restrict__ e = E + s * nfr_cap;
   const int tid = threadIdx.x;
   auto bsum = [&](double v) {
@@ -155,9 +152,9 @@ __global__ void __launch_bounds__(256) ta_crude(int64_t B, int64_t L, const int3
   __shared__ float er[ENV_LDS], ed[ENV_LDS];
   __shared__ float bv[256];
   __shared__ int bj[256];
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.y * 65535;
+  const int64_t b = grid_row_xy();
   if (b >= B) return;
-  const int nfr = (int)(row_len(lengths, b, L) / FRAME);
+  const int nfr = (int)(row_length(lengths, b, L) / FRAME);
   const int tid = threadIdx.x;
   const float *gr = E + b * nfr_cap, *gd = E + (B + b) * nfr_cap;
   const bool in_lds = nfr <= ENV_LDS;
@@ -244,7 +241,7 @@ __device__ __forceinline__ SlotRange slot_range(int64_t blk, int64_t B, int64_t 
   r.c = (int)(ut.desc ? blk / B : blk % nchunk);
   r.valid = r.b < B;
   if (!r.valid) return r;
-  r.Lr = row_len(lengths, r.b, L);
+  r.Lr = row_length(lengths, r.b, L);
   r.n0 = (int64_t)r.c * CS;
   r.hi = r.n0 + CS;
   r.lag0 = crude ? (int64_t)crude[r.b] - FINE : 0;  // crude: NULL with slot descriptors
@@ -501,7 +498,7 @@ __global__ void __launch_bounds__(256) ta_fine_pick(int64_t B, const int *__rest
                                                     const float *__restrict__ part, int *__restrict__ delay) {
   __shared__ double bv[256];
   __shared__ int bj[256];
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.y * 65535;
+  const int64_t b = grid_row_xy();
   if (b >= B) return;
   const int tid = threadIdx.x;
   double best = 0.0;
@@ -536,11 +533,11 @@ __global__ void __launch_bounds__(256) ta_fine_pick(int64_t B, const int *__rest
 __global__ void __launch_bounds__(256) ta_shift(const float *__restrict__ deg, int64_t B, int64_t L, int64_t ld,
                                                 const int32_t *__restrict__ lengths, const int *__restrict__ delay,
                                                 float *__restrict__ out, int64_t ld_out) {
-  const int64_t b = blockIdx.y + (int64_t)blockIdx.z * 65535;
+  const int64_t b = grid_row_yz();
   if (b >= B) return;
   const int64_t n = 4 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
   if (n >= L) return;
-  const int64_t Lr = row_len(lengths, b, L);
+  const int64_t Lr = row_length(lengths, b, L);
   const int64_t D = delay[b];
   const float *y = deg + b * ld;
   float v[4];
@@ -568,10 +565,10 @@ __global__ void __launch_bounds__(64) ta_utterances(int64_t B, int64_t L, const 
                                                     int *__restrict__ nutt, int *__restrict__ utt,
                                                     int *__restrict__ reg, int *__restrict__ cs) {
   __shared__ int us[2 * MAXU];
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.y * 65535;
+  const int64_t b = grid_row_xy();
   if (b >= B) return;
   const int lane = threadIdx.x;
-  const int64_t Lr = row_len(lengths, b, L);
+  const int64_t Lr = row_length(lengths, b, L);
   const int nfr = (int)(Lr / FRAME);
   const float *env = E + b * nfr_cap;
   int n = 0, s0 = -1, e0 = -1, rs = -1;  // utterances, joined run [s0, e0), open raw run from rs
@@ -684,9 +681,9 @@ __global__ void __launch_bounds__(256) ta_crude_utt(int64_t B, int64_t L, const 
   __shared__ int sj[4];
   __shared__ float sr[UTT_LDS], sd[UTT_LDS + 2 * SEARCHBUF + 1];
   const int u = blockIdx.y;  // rows fastest in the dispatch order: a row's active workgroups spread over the XCDs
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.z * 65535;
+  const int64_t b = grid_row_xz();
   if (b >= B || u >= nutt[b]) return;
-  const int nfr = (int)(row_len(lengths, b, L) / FRAME);
+  const int nfr = (int)(row_length(lengths, b, L) / FRAME);
   const int M = nfr < 2 ? 0 : min(max_frames, nfr - 1);
   const int jrow = crude[b] / FRAME;
   const int jlo = max(-M, jrow - SEARCHBUF), jhi = min(M, jrow + SEARCHBUF);
@@ -740,7 +737,7 @@ __global__ void __launch_bounds__(256) ta_pick_utt(int64_t B, const int *__restr
   __shared__ double sv[4];
   __shared__ int sj[4];
   const int u = blockIdx.y;  // rows fastest in the dispatch order: a row's active workgroups spread over the XCDs
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.z * 65535;
+  const int64_t b = grid_row_xz();
   if (b >= B || u >= nutt[b]) return;
   const int tid = threadIdx.x;
   const int c0 = cs[b * (MAXU + 1) + u], m = cs[b * (MAXU + 1) + u + 1] - c0;
@@ -834,7 +831,7 @@ __global__ void __launch_bounds__(64) ta_segments(int64_t B, int64_t L, const in
     add(rg[u], o[2]);
     if (o[0] == 2) add(rg[u] + o[1], o[3]);
   }
-  st[n] = (int)row_len(lengths, b, L);
+  st[n] = (int)row_length(lengths, b, L);
   int best = -1, d = 0;
   for (int k = 0; k < n; ++k)
     if (st[k + 1] - st[k] > best) {
@@ -852,7 +849,7 @@ __global__ void __launch_bounds__(256) ta_shift_seg(const float *__restrict__ de
                                                     const int *__restrict__ seg_delay, float *__restrict__ out,
                                                     int64_t ld_out) {
   __shared__ int st[MAXSEG + 1], dl[MAXSEG];
-  const int64_t b = blockIdx.y + (int64_t)blockIdx.z * 65535;
+  const int64_t b = grid_row_yz();
   if (b >= B) return;
   const int n_s = nseg[b];
   if (threadIdx.x <= n_s) st[threadIdx.x] = seg_start[b * (MAXSEG + 1) + threadIdx.x];
@@ -860,7 +857,7 @@ __global__ void __launch_bounds__(256) ta_shift_seg(const float *__restrict__ de
   __syncthreads();
   const int64_t n = 4 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
   if (n >= L) return;
-  const int64_t Lr = row_len(lengths, b, L);
+  const int64_t Lr = row_length(lengths, b, L);
   const float *y = deg + b * ld;
   int k = 0;
   while (k + 1 < n_s && st[k + 1] <= n) ++k;
@@ -928,7 +925,7 @@ __global__ void __launch_bounds__(256) ta_pick_p862(int64_t B, const int *__rest
   __shared__ double pw[PCACHE];                 // a piece's vote, 0 if it does not vote
   __shared__ int pg[PCACHE];                    // its lag index, -1 if it does not vote
   const int u = blockIdx.y;  // rows fastest in the dispatch order: a row's active workgroups spread over the XCDs
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.z * 65535;
+  const int64_t b = grid_row_xz();
   if (b >= B || u >= nutt[b]) return;
   const int tid = threadIdx.x;
   const int c0 = cs[b * (MAXU + 1) + u], m = cs[b * (MAXU + 1) + u + 1] - c0;
@@ -1087,7 +1084,7 @@ __global__ void __launch_bounds__(64) ta_segments_p862(int64_t B, int64_t L, con
       ++n;
     }
   }
-  st[n] = (int)row_len(lengths, b, L);
+  st[n] = (int)row_length(lengths, b, L);
   int best = -1, d = 0;
   for (int k = 0; k < n; ++k)
     if (st[k + 1] - st[k] > best) {
@@ -1124,10 +1121,10 @@ __global__ void __launch_bounds__(64) ta_bad_find(int64_t B, int64_t L, const in
                                                   int *__restrict__ bad, int4 *__restrict__ desc,
                                                   int *__restrict__ ndesc, int *__restrict__ cs_bad, int nslot) {
   __shared__ int iv[2 * MAXBAD];
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.y * 65535;
+  const int64_t b = grid_row_xy();
   if (b >= B) return;
   const int lane = threadIdx.x;
-  const int64_t Lr = row_len(lengths, b, L);
+  const int64_t Lr = row_length(lengths, b, L);
   const int F = std::min<int64_t>(pesq_frames_of(Lr), Fcap);
   const float *sym = frames + 2 * b * Fcap;
   int n = 0, s0 = -1, e0 = -1, rs = -1;  // intervals, joined run [s0, e0), open raw run from rs
@@ -1203,7 +1200,7 @@ __global__ void __launch_bounds__(256) ta_bad_pick(int64_t B, const int *__restr
   __shared__ double sv[4];
   __shared__ int sj[4];
   const int i = blockIdx.y;  // rows fastest in the dispatch order: a row's active workgroups spread over the XCDs
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.z * 65535;
+  const int64_t b = grid_row_xz();
   if (b >= B || i >= n_bad[b]) return;
   const int tid = threadIdx.x;
   const int c0 = cs_bad[b * (MAXBAD + 1) + i], m = cs_bad[b * (MAXBAD + 1) + i + 1] - c0;
@@ -1236,9 +1233,9 @@ __global__ void __launch_bounds__(256) ta_bad_shift(const float *__restrict__ de
                                                     const int *__restrict__ n_bad, const int *__restrict__ bad,
                                                     float *out, int64_t ld_out) {
   __shared__ int lo[MAXBAD], hi[MAXBAD], dl[MAXBAD];
-  const int64_t b = blockIdx.y + (int64_t)blockIdx.z * 65535;
+  const int64_t b = grid_row_yz();
   if (b >= B) return;
-  const int64_t Lr = row_len(lengths, b, L);
+  const int64_t Lr = row_length(lengths, b, L);
   const int nb = n_bad[b];
   if (threadIdx.x < nb) {
     const int *o = bad + (b * MAXBAD + threadIdx.x) * 3;
@@ -1281,10 +1278,10 @@ __global__ void __launch_bounds__(64) ta_bad_pool(const float *__restrict__ fram
                                                   const int *__restrict__ n_bad, const int *__restrict__ bad,
                                                   float *__restrict__ mos) {
   __shared__ int f0s[MAXBAD], f1s[MAXBAD];
-  const int64_t b = blockIdx.x + (int64_t)blockIdx.y * 65535;
+  const int64_t b = grid_row_xy();
   if (b >= B) return;
   const int lane = threadIdx.x;
-  const int64_t Lr = row_len(lengths, b, L);
+  const int64_t Lr = row_length(lengths, b, L);
   const int F = std::min<int64_t>(pesq_frames_of(Lr), Fcap);
   if (F < 20 || !__builtin_isfinite(dist[b])) {
     if (lane == 0) mos[b] = __builtin_nanf("");
@@ -1340,94 +1337,60 @@ __global__ void __launch_bounds__(64) ta_bad_pool(const float *__restrict__ fram
 }
 
 
-inline int64_t frames_cap(int64_t L) { return L / FRAME; }
+inline int64_t env_cap(int64_t L) { return std::max<int64_t>(L / FRAME, 1); }  // envelope frames per signal
 inline int64_t nchunks(int64_t L) { return (L + CS - 1) / CS; }
+// 64-bit: max_delay may be INT32_MAX (alignment.py clamps to it), where the 32-bit sum would wrap
+inline int lag_frames(int32_t max_delay) {
+  return (int)std::min<int64_t>(((int64_t)max_delay + FRAME - 1) / FRAME, (int64_t)INT32_MAX);
+}
 
+// Workspaces: one layout function per mode (Arena, fsem_common.h).
 struct Ws {
   float *E;
   int *crude;
-  float *part;
   int *delay;  // internal when the caller passes no delay array
+  float *part;
 };
-
-inline size_t ws_bytes(int64_t B, int64_t L) {
-  const size_t e = align_up((size_t)(2 * B * std::max<int64_t>(frames_cap(L), 1)) * 4, 256);
-  const size_t cr = align_up((size_t)B * 4, 256);
-  const size_t pt = align_up((size_t)(B * nchunks(L) * NGRP * LG) * 4, 256);
-  return e + 2 * cr + pt;
-}
-
-inline Ws carve(void *ws, int64_t B, int64_t L) {
-  char *p = static_cast<char *>(ws);
+inline Ws layout(Arena &a, int64_t B, int64_t L) {
   Ws w;
-  w.E = reinterpret_cast<float *>(p);
-  p += align_up((size_t)(2 * B * std::max<int64_t>(frames_cap(L), 1)) * 4, 256);
-  w.crude = reinterpret_cast<int *>(p);
-  p += align_up((size_t)B * 4, 256);
-  w.delay = reinterpret_cast<int *>(p);
-  p += align_up((size_t)B * 4, 256);
-  w.part = reinterpret_cast<float *>(p);
+  w.E = a.take<float>(2 * B * env_cap(L));
+  w.crude = a.take<int>(B);
+  w.delay = a.take<int>(B);
+  w.part = a.take<float>(B * nchunks(L) * NGRP * LG);
   return w;
 }
 
 // utterance mode: the row-mode arrays (E, crude, internal delay; part with nslot pieces per row)
-// plus the utterance tables and the internal segment outputs
+// plus the utterance tables and the internal segment outputs; the P.862 mode continues the same
+// arena with the pieces' peaks and its wider segment table (null in the utterance mode)
 inline int64_t nslots(int64_t L) { return nchunks(L) + MAXU; }
 struct UttWs {
   float *E, *part;
-  int *crude, *delay, *nutt, *utt, *reg, *cs, *ucrude, *useg, *nseg, *seg_start, *seg_delay;
-};
-inline size_t utt_ws_bytes(int64_t B, int64_t L) {
-  auto ints = [B](int64_t per_row) { return align_up((size_t)(B * per_row) * 4, 256); };
-  return align_up((size_t)(2 * B * std::max<int64_t>(frames_cap(L), 1)) * 4, 256) +
-         align_up((size_t)(B * nslots(L) * NGRP * LG) * 4, 256) + ints(1) * 4 + ints(2 * MAXU) +
-         2 * ints(MAXU + 1) + ints(MAXU) + ints(4 * MAXU) + ints(MAXSEG + 1) + ints(MAXSEG);
-}
-inline UttWs utt_carve(void *ws, int64_t B, int64_t L) {
-  char *p = static_cast<char *>(ws);
-  UttWs w;
-  auto take = [&](size_t bytes) {
-    char *q = p;
-    p += align_up(bytes, 256);
-    return q;
-  };
-  w.E = reinterpret_cast<float *>(take((size_t)(2 * B * std::max<int64_t>(frames_cap(L), 1)) * 4));
-  w.part = reinterpret_cast<float *>(take((size_t)(B * nslots(L) * NGRP * LG) * 4));
-  auto ti = [&](int64_t per_row) { return reinterpret_cast<int *>(take((size_t)(B * per_row) * 4)); };
-  w.crude = ti(1);
-  w.delay = ti(1);
-  w.nutt = ti(1);
-  w.nseg = ti(1);
-  w.utt = ti(2 * MAXU);
-  w.reg = ti(MAXU + 1);
-  w.cs = ti(MAXU + 1);
-  w.ucrude = ti(MAXU);
-  w.useg = ti(4 * MAXU);
-  w.seg_start = ti(MAXSEG + 1);
-  w.seg_delay = ti(MAXSEG);
-  return w;
-}
-
-// P.862 mode: the utterance-mode workspace, then the pieces' peaks and the wider segment table
-struct P862Ws {
+  int *crude, *delay, *nutt, *nseg, *utt, *reg, *cs, *ucrude, *useg, *seg_start, *seg_delay;
   float *pv;
-  int *pl, *useg;
+  int *pl, *useg_p;
   double *pw;
 };
-inline size_t p862_ws_bytes(int64_t B, int64_t L) {
-  return utt_ws_bytes(B, L) + 2 * align_up((size_t)(B * nslots(L)) * 4, 256) +
-         align_up((size_t)(B * MAXU * USEG_P) * 4, 256) + align_up((size_t)(B * nslots(L)) * 8, 256);
-}
-inline P862Ws p862_carve(void *ws, int64_t B, int64_t L) {
-  char *p = static_cast<char *>(ws) + utt_ws_bytes(B, L);
-  P862Ws w;
-  w.pv = reinterpret_cast<float *>(p);
-  p += align_up((size_t)(B * nslots(L)) * 4, 256);
-  w.pl = reinterpret_cast<int *>(p);
-  p += align_up((size_t)(B * nslots(L)) * 4, 256);
-  w.useg = reinterpret_cast<int *>(p);
-  p += align_up((size_t)(B * MAXU * USEG_P) * 4, 256);
-  w.pw = reinterpret_cast<double *>(p);
+inline UttWs utt_layout(Arena &a, int64_t B, int64_t L, bool p862) {
+  UttWs w{};
+  w.E = a.take<float>(2 * B * env_cap(L));
+  w.part = a.take<float>(B * nslots(L) * NGRP * LG);
+  w.crude = a.take<int>(B);
+  w.delay = a.take<int>(B);
+  w.nutt = a.take<int>(B);
+  w.nseg = a.take<int>(B);
+  w.utt = a.take<int>(B * 2 * MAXU);
+  w.reg = a.take<int>(B * (MAXU + 1));
+  w.cs = a.take<int>(B * (MAXU + 1));
+  w.ucrude = a.take<int>(B * MAXU);
+  w.useg = a.take<int>(B * 4 * MAXU);
+  w.seg_start = a.take<int>(B * (MAXSEG + 1));
+  w.seg_delay = a.take<int>(B * MAXSEG);
+  if (!p862) return w;
+  w.pv = a.take<float>(B * nslots(L));
+  w.pl = a.take<int>(B * nslots(L));
+  w.useg_p = a.take<int>(B * MAXU * USEG_P);
+  w.pw = a.take<double>(B * nslots(L));
   return w;
 }
 
@@ -1439,21 +1402,34 @@ struct BadWs {
   int *ndesc, *cs;
   float *part;
 };
-inline size_t bad_ws_bytes(int64_t B, int64_t L) {
-  return align_up((size_t)(B * bad_nslots(L)) * sizeof(int4), 256) + align_up((size_t)B * 4, 256) +
-         align_up((size_t)(B * (MAXBAD + 1)) * 4, 256) + align_up((size_t)(B * bad_nslots(L) * NGRP * LG) * 4, 256);
-}
-inline BadWs bad_carve(void *ws, int64_t B, int64_t L) {
-  char *p = static_cast<char *>(ws);
+inline BadWs bad_layout(Arena &a, int64_t B, int64_t L) {
   BadWs w;
-  w.desc = reinterpret_cast<int4 *>(p);
-  p += align_up((size_t)(B * bad_nslots(L)) * sizeof(int4), 256);
-  w.ndesc = reinterpret_cast<int *>(p);
-  p += align_up((size_t)B * 4, 256);
-  w.cs = reinterpret_cast<int *>(p);
-  p += align_up((size_t)(B * (MAXBAD + 1)) * 4, 256);
-  w.part = reinterpret_cast<float *>(p);
+  w.desc = a.take<int4>(B * bad_nslots(L));
+  w.ndesc = a.take<int>(B);
+  w.cs = a.take<int>(B * (MAXBAD + 1));
+  w.part = a.take<float>(B * bad_nslots(L) * NGRP * LG);
   return w;
+}
+
+// What the row mode and the segmented modes share.  The argument checks (`pieces`: fine-stage
+// pieces per row, whose batch total is a 32-bit grid size) ...
+inline bool args_ok(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld, int32_t max_delay,
+                    const float *deg_aligned, int64_t ld_out, int64_t pieces) {
+  return ref && deg && batch > 0 && length > 0 && ld >= length && length <= kMaxLength && max_delay >= 0 &&
+         (!deg_aligned || (ld_out >= length && ld_out % 4 == 0)) && ld % 4 == 0 && batch * pieces <= INT32_MAX;
+}
+// ... and stages 1-2: frame energies, envelopes, the rows' crude lags.
+inline int launch_crude(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                        const int32_t *lengths, int32_t max_delay, float *E, int *crude, hipStream_t st) {
+  const int64_t nfr_cap = env_cap(length);
+  ta_energy<<<grid_yz((unsigned)((nfr_cap + 15) / 16), 2 * batch), 256, 0, st>>>(ref, deg, batch, length, ld, lengths,
+                                                                                E, nfr_cap);
+  FSEM_CHECK_LAUNCH();
+  ta_envelope<<<grid_xy(2 * batch), 256, 0, st>>>(batch, length, lengths, E, nfr_cap);
+  FSEM_CHECK_LAUNCH();
+  ta_crude<<<grid_xy(batch), 256, 0, st>>>(batch, length, lengths, E, nfr_cap, lag_frames(max_delay), crude);
+  FSEM_CHECK_LAUNCH();
+  return FSEM_OK;
 }
 
 }  // namespace align
@@ -1463,55 +1439,47 @@ using namespace fsem;
 
 extern "C" size_t fsem_time_align_workspace_bytes(int64_t batch, int64_t length) {
   if (batch <= 0 || length <= 0) return 0;
-  return align::ws_bytes(batch, length);
+  return layout_bytes(align::layout, batch, length);
 }
 
 extern "C" int fsem_time_align_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
                                    const int32_t *lengths, int32_t max_delay, int32_t *delay, float *deg_aligned,
                                    int64_t ld_out, void *ws, size_t ws_bytes, void *stream) {
-  if (!ref || !deg || batch <= 0 || length <= 0 || ld < length || length > kMaxLength || max_delay < 0 ||
-      (deg_aligned && (ld_out < length || ld_out % 4 != 0)) || (!delay && !deg_aligned) || (ld % 4) != 0)
+  if (!align::args_ok(ref, deg, batch, length, ld, max_delay, deg_aligned, ld_out, align::nchunks(length)) ||
+      (!delay && !deg_aligned))
     return FSEM_EINVAL;
-  const int64_t nch = align::nchunks(length);
-  if (batch * nch > INT32_MAX) return FSEM_EINVAL;
-  if (!ws || ws_bytes < align::ws_bytes(batch, length)) return FSEM_EWORKSPACE;
+  Arena a(ws);
+  const align::Ws w = align::layout(a, batch, length);
+  if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  align::Ws w = align::carve(ws, batch, length);
   int *dl = delay ? delay : w.delay;
-  const int64_t nfr_cap = std::max<int64_t>(align::frames_cap(length), 1);
-  const int64_t sig = 2 * batch;
-  // 64-bit: max_delay may be INT32_MAX (alignment.py clamps to it), where the 32-bit sum would wrap
-  const int max_frames =
-      (int)std::min<int64_t>(((int64_t)max_delay + align::FRAME - 1) / align::FRAME, (int64_t)INT32_MAX);
-  auto yz = [](int64_t n) { return dim3(1, (unsigned)std::min<int64_t>(n, 65535), (unsigned)((n + 65534) / 65535)); };
-  {
-    dim3 grid = yz(sig);
-    grid.x = (unsigned)((nfr_cap + 15) / 16);
-    align::ta_energy<<<grid, 256, 0, st>>>(ref, deg, batch, length, ld, lengths, w.E, nfr_cap);
-    FSEM_CHECK_LAUNCH();
-  }
-  auto xy = [](int64_t n) { return dim3((unsigned)std::min<int64_t>(n, 65535), (unsigned)((n + 65534) / 65535)); };
-  align::ta_envelope<<<xy(sig), 256, 0, st>>>(batch, length, lengths, w.E, nfr_cap);
-  FSEM_CHECK_LAUNCH();
-  align::ta_crude<<<xy(batch), 256, 0, st>>>(batch, length, lengths, w.E, nfr_cap, max_frames, w.crude);
-  FSEM_CHECK_LAUNCH();
+  const int64_t nch = align::nchunks(length);
+  const int rc = align::launch_crude(ref, deg, batch, length, ld, lengths, max_delay, w.E, w.crude, st);
+  if (rc != FSEM_OK) return rc;
   align::launch_fine((unsigned)(batch * nch), st, ref, deg, batch, length, ld, lengths, w.crude, (int)nch, w.part,
                      align::UttTables{});
   FSEM_CHECK_LAUNCH();
-  align::ta_fine_pick<<<xy(batch), 256, 0, st>>>(batch, w.crude, (int)nch, w.part, dl);
+  align::ta_fine_pick<<<grid_xy(batch), 256, 0, st>>>(batch, w.crude, (int)nch, w.part, dl);
   FSEM_CHECK_LAUNCH();
   if (deg_aligned) {
-    dim3 grid = yz(batch);
-    grid.x = (unsigned)((length + 1023) / 1024);
-    align::ta_shift<<<grid, 256, 0, st>>>(deg, batch, length, ld, lengths, dl, deg_aligned, ld_out);
+    align::ta_shift<<<grid_yz((unsigned)((length + 1023) / 1024), batch), 256, 0, st>>>(deg, batch, length, ld, lengths,
+                                                                                       dl, deg_aligned, ld_out);
     FSEM_CHECK_LAUNCH();
   }
   return FSEM_OK;
 }
 
-extern "C" size_t fsem_time_align_utt_workspace_bytes(int64_t batch, int64_t length) {
+static size_t segmented_workspace_bytes(bool p862, int64_t batch, int64_t length) {
   if (batch <= 0 || length <= 0) return 0;
-  return align::utt_ws_bytes(batch, length);
+  return layout_bytes(align::utt_layout, batch, length, p862);
+}
+
+extern "C" size_t fsem_time_align_utt_workspace_bytes(int64_t batch, int64_t length) {
+  return segmented_workspace_bytes(false, batch, length);
+}
+
+extern "C" size_t fsem_time_align_p862_workspace_bytes(int64_t batch, int64_t length) {
+  return segmented_workspace_bytes(true, batch, length);
 }
 
 // the utterance and P.862 modes (stages 1-2, 5-7, then 8 or 10-12, then 9)
@@ -1519,70 +1487,49 @@ static int time_align_segmented(bool p862, const float *ref, const float *deg, i
                                 int64_t ld, const int32_t *lengths, int32_t max_delay, int32_t *delay,
                                 int32_t *n_seg, int32_t *seg_start, int32_t *seg_delay, float *deg_aligned,
                                 int64_t ld_out, void *ws, size_t ws_bytes, void *stream) {
-  if (!ref || !deg || batch <= 0 || length <= 0 || ld < length || length > kMaxLength || max_delay < 0 ||
-      (deg_aligned && (ld_out < length || ld_out % 4 != 0)) || (ld % 4) != 0 ||
+  if (!align::args_ok(ref, deg, batch, length, ld, max_delay, deg_aligned, ld_out, align::nslots(length)) ||
       (!delay && !n_seg && !deg_aligned) || ((n_seg != nullptr) != (seg_start != nullptr)) ||
       ((n_seg != nullptr) != (seg_delay != nullptr)))
     return FSEM_EINVAL;
-  const int64_t nsl = align::nslots(length);
-  if (batch * nsl > INT32_MAX) return FSEM_EINVAL;
-  if (!ws || ws_bytes < (p862 ? align::p862_ws_bytes(batch, length) : align::utt_ws_bytes(batch, length)))
-    return FSEM_EWORKSPACE;
+  Arena a(ws);
+  const align::UttWs w = align::utt_layout(a, batch, length, p862);
+  if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  align::UttWs w = align::utt_carve(ws, batch, length);
   int *dl = delay ? delay : w.delay;
   int *ns = n_seg ? n_seg : w.nseg;
   int *ss = seg_start ? seg_start : w.seg_start;
   int *sd = seg_delay ? seg_delay : w.seg_delay;
-  const int64_t nfr_cap = std::max<int64_t>(align::frames_cap(length), 1);
-  const int64_t sig = 2 * batch;
-  const int max_frames =
-      (int)std::min<int64_t>(((int64_t)max_delay + align::FRAME - 1) / align::FRAME, (int64_t)INT32_MAX);
-  auto yz = [](int64_t n) { return dim3(1, (unsigned)std::min<int64_t>(n, 65535), (unsigned)((n + 65534) / 65535)); };
-  auto xy = [](int64_t n) { return dim3((unsigned)std::min<int64_t>(n, 65535), (unsigned)((n + 65534) / 65535)); };
-  {
-    dim3 grid = yz(sig);
-    grid.x = (unsigned)((nfr_cap + 15) / 16);
-    align::ta_energy<<<grid, 256, 0, st>>>(ref, deg, batch, length, ld, lengths, w.E, nfr_cap);
-    FSEM_CHECK_LAUNCH();
-  }
-  align::ta_envelope<<<xy(sig), 256, 0, st>>>(batch, length, lengths, w.E, nfr_cap);
+  const int64_t nsl = align::nslots(length);
+  const int64_t nfr_cap = align::env_cap(length);
+  const int rc = align::launch_crude(ref, deg, batch, length, ld, lengths, max_delay, w.E, w.crude, st);
+  if (rc != FSEM_OK) return rc;
+  align::ta_utterances<<<grid_xy(batch), 64, 0, st>>>(batch, length, lengths, w.E, nfr_cap, w.nutt, w.utt, w.reg, w.cs);
   FSEM_CHECK_LAUNCH();
-  align::ta_crude<<<xy(batch), 256, 0, st>>>(batch, length, lengths, w.E, nfr_cap, max_frames, w.crude);
+  const dim3 per_utt = grid_xz(batch, align::MAXU);
+  align::ta_crude_utt<<<per_utt, 256, 0, st>>>(batch, length, lengths, w.E, nfr_cap, align::lag_frames(max_delay),
+                                               w.crude, w.nutt, w.utt, w.ucrude);
   FSEM_CHECK_LAUNCH();
-  align::ta_utterances<<<xy(batch), 64, 0, st>>>(batch, length, lengths, w.E, nfr_cap, w.nutt, w.utt, w.reg, w.cs);
-  FSEM_CHECK_LAUNCH();
-  {
-    const dim3 grid((unsigned)std::min<int64_t>(batch, 65535), align::MAXU, (unsigned)((batch + 65534) / 65535));
-    align::ta_crude_utt<<<grid, 256, 0, st>>>(batch, length, lengths, w.E, nfr_cap, max_frames, w.crude, w.nutt,
-                                              w.utt, w.ucrude);
-    FSEM_CHECK_LAUNCH();
-  }
   align::launch_fine((unsigned)(batch * nsl), st, ref, deg, batch, length, ld, lengths, w.crude, (int)nsl, w.part,
                      align::UttTables{w.nutt, w.reg, w.cs, w.ucrude});
   FSEM_CHECK_LAUNCH();
   if (p862) {
-    const align::P862Ws q = align::p862_carve(ws, batch, length);
-    align::ta_piece_peaks<<<(unsigned)((batch * nsl + 3) / 4), 256, 0, st>>>(batch * nsl, w.part, q.pv, q.pl, q.pw);
+    align::ta_piece_peaks<<<(unsigned)((batch * nsl + 3) / 4), 256, 0, st>>>(batch * nsl, w.part, w.pv, w.pl, w.pw);
     FSEM_CHECK_LAUNCH();
-    const dim3 grid((unsigned)std::min<int64_t>(batch, 65535), align::MAXU, (unsigned)((batch + 65534) / 65535));
-    align::ta_pick_p862<<<grid, 256, 0, st>>>(batch, w.nutt, w.cs, w.ucrude, (int)nsl, q.pv, q.pl, q.pw, q.useg);
+    align::ta_pick_p862<<<per_utt, 256, 0, st>>>(batch, w.nutt, w.cs, w.ucrude, (int)nsl, w.pv, w.pl, w.pw, w.useg_p);
     FSEM_CHECK_LAUNCH();
     align::ta_segments_p862<<<(unsigned)((batch + 63) / 64), 64, 0, st>>>(batch, length, lengths, w.nutt, w.reg,
-                                                                          q.useg, ns, ss, sd, dl);
+                                                                          w.useg_p, ns, ss, sd, dl);
     FSEM_CHECK_LAUNCH();
   } else {
-    const dim3 grid((unsigned)std::min<int64_t>(batch, 65535), align::MAXU, (unsigned)((batch + 65534) / 65535));
-    align::ta_pick_utt<<<grid, 256, 0, st>>>(batch, w.nutt, w.cs, w.ucrude, (int)nsl, w.part, w.useg);
+    align::ta_pick_utt<<<per_utt, 256, 0, st>>>(batch, w.nutt, w.cs, w.ucrude, (int)nsl, w.part, w.useg);
     FSEM_CHECK_LAUNCH();
     align::ta_segments<<<(unsigned)((batch + 63) / 64), 64, 0, st>>>(batch, length, lengths, w.nutt, w.reg, w.useg,
                                                                    ns, ss, sd, dl);
     FSEM_CHECK_LAUNCH();
   }
   if (deg_aligned) {
-    dim3 grid = yz(batch);
-    grid.x = (unsigned)((length + 1023) / 1024);
-    align::ta_shift_seg<<<grid, 256, 0, st>>>(deg, batch, length, ld, lengths, ns, ss, sd, deg_aligned, ld_out);
+    align::ta_shift_seg<<<grid_yz((unsigned)((length + 1023) / 1024), batch), 256, 0, st>>>(
+        deg, batch, length, ld, lengths, ns, ss, sd, deg_aligned, ld_out);
     FSEM_CHECK_LAUNCH();
   }
   return FSEM_OK;
@@ -1597,11 +1544,6 @@ extern "C" int fsem_time_align_utt_f32(const float *ref, const float *deg, int64
                               seg_delay, deg_aligned, ld_out, ws, ws_bytes, stream);
 }
 
-extern "C" size_t fsem_time_align_p862_workspace_bytes(int64_t batch, int64_t length) {
-  if (batch <= 0 || length <= 0) return 0;
-  return align::p862_ws_bytes(batch, length);
-}
-
 extern "C" int fsem_time_align_p862_f32(const float *ref, const float *deg, int64_t batch, int64_t length,
                                         int64_t ld, const int32_t *lengths, int32_t max_delay, int32_t *delay,
                                         int32_t *n_seg, int32_t *seg_start, int32_t *seg_delay,
@@ -1613,7 +1555,7 @@ extern "C" int fsem_time_align_p862_f32(const float *ref, const float *deg, int6
 
 extern "C" size_t fsem_pesq_bad_intervals_workspace_bytes(int64_t batch, int64_t length) {
   if (batch <= 0 || length <= 0) return 0;
-  return align::bad_ws_bytes(batch, length);
+  return layout_bytes(align::bad_layout, batch, length);
 }
 
 extern "C" int fsem_pesq_bad_intervals_f32(const float *ref, const float *deg, const float *deg_aligned,
@@ -1628,14 +1570,13 @@ extern "C" int fsem_pesq_bad_intervals_f32(const float *ref, const float *deg, c
     return FSEM_EINVAL;
   const int64_t nsl = align::bad_nslots(length);
   if (batch * nsl > INT32_MAX) return FSEM_EINVAL;
-  if (!ws || ws_bytes < align::bad_ws_bytes(batch, length)) return FSEM_EWORKSPACE;
+  Arena a(ws);
+  const align::BadWs w = align::bad_layout(a, batch, length);
+  if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const align::BadWs w = align::bad_carve(ws, batch, length);
   const int64_t Fcap = align::pesq_frames_of(length);
-  auto yz = [](int64_t n) { return dim3(1, (unsigned)std::min<int64_t>(n, 65535), (unsigned)((n + 65534) / 65535)); };
-  auto xy = [](int64_t n) { return dim3((unsigned)std::min<int64_t>(n, 65535), (unsigned)((n + 65534) / 65535)); };
-  align::ta_bad_find<<<xy(batch), 64, 0, st>>>(batch, length, lengths, frames, Fcap, n_seg, seg_start, seg_delay,
-                                               n_bad, bad, w.desc, w.ndesc, w.cs, (int)nsl);
+  align::ta_bad_find<<<grid_xy(batch), 64, 0, st>>>(batch, length, lengths, frames, Fcap, n_seg, seg_start, seg_delay,
+                                                    n_bad, bad, w.desc, w.ndesc, w.cs, (int)nsl);
   FSEM_CHECK_LAUNCH();
   align::UttTables ut{};
   ut.desc = w.desc;
@@ -1643,18 +1584,11 @@ extern "C" int fsem_pesq_bad_intervals_f32(const float *ref, const float *deg, c
   align::launch_fine((unsigned)(batch * nsl), st, ref, deg, batch, length, ld, lengths, nullptr, (int)nsl, w.part,
                      ut);
   FSEM_CHECK_LAUNCH();
-  {
-    const dim3 grid((unsigned)std::min<int64_t>(batch, 65535), align::MAXBAD, (unsigned)((batch + 65534) / 65535));
-    align::ta_bad_pick<<<grid, 256, 0, st>>>(batch, n_bad, w.cs, (int)nsl, w.part, bad);
-    FSEM_CHECK_LAUNCH();
-  }
-  {
-    dim3 grid = yz(batch);
-    grid.x = (unsigned)((length + 1023) / 1024);
-    align::ta_bad_shift<<<grid, 256, 0, st>>>(deg, deg_aligned, batch, length, ld, lengths, n_bad, bad, deg_second,
-                                              ld_out);
-    FSEM_CHECK_LAUNCH();
-  }
+  align::ta_bad_pick<<<grid_xz(batch, align::MAXBAD), 256, 0, st>>>(batch, n_bad, w.cs, (int)nsl, w.part, bad);
+  FSEM_CHECK_LAUNCH();
+  align::ta_bad_shift<<<grid_yz((unsigned)((length + 1023) / 1024), batch), 256, 0, st>>>(
+      deg, deg_aligned, batch, length, ld, lengths, n_bad, bad, deg_second, ld_out);
+  FSEM_CHECK_LAUNCH();
   return FSEM_OK;
 }
 
@@ -1665,9 +1599,8 @@ extern "C" int fsem_pesq_pool_f32(const float *frames, const float *frames2, con
     return FSEM_EINVAL;
   const int64_t Fcap = align::pesq_frames_of(length);
   if (Fcap < 20 && !lengths) return FSEM_ESHORT;
-  auto xy = [](int64_t n) { return dim3((unsigned)std::min<int64_t>(n, 65535), (unsigned)((n + 65534) / 65535)); };
-  align::ta_bad_pool<<<xy(batch), 64, 0, (hipStream_t)stream>>>(frames, frames2, dist, batch, length, Fcap, lengths,
-                                                                 n_bad, bad, mos);
+  align::ta_bad_pool<<<grid_xy(batch), 64, 0, (hipStream_t)stream>>>(frames, frames2, dist, batch, length, Fcap,
+                                                                      lengths, n_bad, bad, mos);
   FSEM_CHECK_LAUNCH();
   return FSEM_OK;
 }

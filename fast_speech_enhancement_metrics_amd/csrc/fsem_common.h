@@ -86,7 +86,53 @@ __device__ __forceinline__ void wave_lds_fence() {
 // Wait for this wave's outstanding LDS stores (before other waves read the data).
 __device__ __forceinline__ void lds_stores_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
+// One DPP move of a 32-bit value under control CTRL (all rows and banks, no bound control).
+template <int CTRL, class T>
+__device__ __forceinline__ T dpp_mov(T v) {
+  static_assert(sizeof(T) == 4, "DPP moves one 32-bit register");
+  return __builtin_bit_cast(T, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
+}
+
+// Row length of utterance b: the per-row length when given (clamped to [0, L]), else L; in L's
+// type (int64_t, or int where the kernel's row arithmetic is 32-bit).
+template <class Len>
+__device__ __forceinline__ Len row_length(const int32_t *__restrict__ lens, int64_t b, Len L) {
+  if (!lens) return L;
+  const Len n = lens[b];
+  return n < 0 ? 0 : (n > L ? L : n);
+}
+
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// A workspace as a sequence of 256-byte aligned regions.  Each entry has one layout function
+// that takes its regions from an Arena in order: run on Arena(nullptr) it measures (bytes() is
+// the entry's *_workspace_bytes), run on Arena(ws) it yields the pointers, so the size and the
+// pointers cannot disagree.
+class Arena {
+ public:
+  explicit Arena(void *base) : base_(static_cast<char *>(base)) {}
+  template <class T>
+  T *take(size_t count) {
+    T *p = base_ ? reinterpret_cast<T *>(base_ + used_) : nullptr;
+    used_ += align_up(count * sizeof(T), 256);
+    return p;
+  }
+  size_t bytes() const { return used_; }
+  // the regions taken so far lie within a workspace of ws_bytes at a non-null base
+  bool fits(size_t ws_bytes) const { return base_ && used_ <= ws_bytes; }
+
+ private:
+  char *base_;
+  size_t used_ = 0;
+};
+
+// The bytes a layout function takes: what the entry's *_workspace_bytes reports.
+template <class Layout, class... Args>
+size_t layout_bytes(Layout layout, const Args &...args) {
+  Arena a(nullptr);
+  layout(a, args...);
+  return a.bytes();
+}
 
 // Longest row any entry accepts (input samples, and 10 / 16 kHz samples after resampling): the
 // kernels address a row with 32-bit byte offsets (raw buffer loads, range-checked descriptors).
@@ -96,5 +142,20 @@ constexpr int64_t kMaxLength = int64_t(1) << 29;
 // Launches that map rows (utterances) to grid.y cover at most kMaxGridY rows each; the host loops
 // over slices [r0, r0 + kMaxGridY) and passes r0 (HIP's grid.y limit, hipDeviceProp maxGridSize[1]).
 constexpr int64_t kMaxGridY = 65535;
+inline dim3 grid_slice(unsigned x, int64_t rows, int64_t r0) {
+  return dim3(x, (unsigned)(rows - r0 < kMaxGridY ? rows - r0 : kMaxGridY));
+}
+
+// Launches that instead fold `rows` over two grid dimensions of at most kMaxGridY each (no host
+// loop): grid_ab spreads them over dimensions a and b, the kernel reads its row with grid_row_ab
+// and returns when it is past the last.  The third dimension is the caller's.
+inline unsigned grid_lo(int64_t rows) { return (unsigned)(rows < kMaxGridY ? rows : kMaxGridY); }
+inline unsigned grid_hi(int64_t rows) { return (unsigned)((rows + kMaxGridY - 1) / kMaxGridY); }
+inline dim3 grid_xy(int64_t rows) { return dim3(grid_lo(rows), grid_hi(rows)); }
+inline dim3 grid_yz(unsigned x, int64_t rows) { return dim3(x, grid_lo(rows), grid_hi(rows)); }
+inline dim3 grid_xz(int64_t rows, unsigned y) { return dim3(grid_lo(rows), y, grid_hi(rows)); }
+__device__ __forceinline__ int64_t grid_row_xy() { return blockIdx.x + (int64_t)blockIdx.y * kMaxGridY; }
+__device__ __forceinline__ int64_t grid_row_yz() { return blockIdx.y + (int64_t)blockIdx.z * kMaxGridY; }
+__device__ __forceinline__ int64_t grid_row_xz() { return blockIdx.x + (int64_t)blockIdx.z * kMaxGridY; }
 
 }  // namespace fsem

@@ -1,7 +1,7 @@
 // Shared geometry of the PESQ front end (pesq.hip) and back end (pesq_back.hip): frames,
 // segments and the band-major Bark layout of a row (PESQ.py:123-140, bark.py:189-204).
 #pragma once
-#include "fsem_common.h"
+#include "fsem_fft.h"  // (fsem_tables.inc: FSEM_PESQ_CH)
 
 namespace fsem {
 namespace pesq {
@@ -43,18 +43,37 @@ __host__ __device__ inline Geometry geometry(int64_t L) {
   return g;
 }
 
-// Row length of utterance b: the per-row length when given (clamped to [0, L]), else L.
-__device__ __forceinline__ int64_t row_length(const int32_t *__restrict__ lens, int64_t b, int64_t L) {
-  if (!lens) return L;
-  const int64_t n = lens[b];
-  return n < 0 ? 0 : (n > L ? L : n);
+// Workspace layouts (Arena, fsem_common.h).
+// Front end: per-segment power partials [2B, nseg, 4], then the range bookkeeping: the segments'
+// range shifts [2B, nseg] (pesq_front's pexp, read by the back end), worklist count, item queue,
+// flags [2B], worklist [2B].
+struct FrontWs {
+  float *ppart;
+  int *rng;
+};
+inline FrontWs front_layout(Arena &a, int64_t batch, int64_t length) {
+  const size_t segs = (size_t)(2 * batch) * (size_t)geometry(length).nseg;
+  FrontWs w;
+  w.ppart = a.take<float>(segs * 4);
+  w.rng = a.take<int>(segs + 2 + 4 * (size_t)batch);
+  return w;
 }
-
-
-// front workspace: per-segment power partials [2B, nseg, 4] float, then the segments' range
-// shifts [2B, nseg] int (pesq_front's pexp)
-inline size_t front_ppart_bytes(int64_t batch, int64_t length) {
-  return align_up(sizeof(float) * (size_t)(2 * batch) * (size_t)geometry(length).nseg * 4, 256);
+// Back end: its scratch rows.
+inline float *back_layout(Arena &a, int64_t batch, int64_t length) {
+  return a.take<float>((size_t)batch * (size_t)geometry(length).F * 4);
+}
+// Whole metric: [front | bark | power | back scratch].
+struct WbWs {
+  FrontWs front;
+  float *bark, *power, *back;
+};
+inline WbWs wb_layout(Arena &a, int64_t batch, int64_t length) {
+  WbWs w;
+  w.front = front_layout(a, batch, length);
+  w.bark = a.take<float>((size_t)(2 * batch) * NBARK * (size_t)bark_ld(geometry(length).F));
+  w.power = a.take<float>((size_t)(2 * batch));
+  w.back = back_layout(a, batch, length);
+  return w;
 }
 
 }  // namespace pesq

@@ -18,11 +18,6 @@
 
 namespace fsem {
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-
 // Squared window quarters of the lane's 4 samples for a block of parity p:
 // {W[64p + 4k + c]^2}, {W[128 + 64p + 4k + c]^2}, k = lane & 15.
 __device__ __forceinline__ void vad_windows(int lane, int p, float4 &wa, float4 &wb) {
@@ -47,10 +42,10 @@ __device__ __forceinline__ float vad_quarter(float4 y, float4 wa, float4 wb, int
   const float sa = pa.x + pa.y, sb = pb.x + pb.y;
   const bool odd = lane & 1;
   float v = odd ? sb : sa;
-  v += dpp_f32<0xB1>(odd ? sa : sb);  // quad_perm [1,0,3,2]: partner's value of my quarter
-  v += dpp_f32<0x4E>(v);              // quad_perm [2,3,0,1]
-  v += dpp_f32<0x124>(v);             // row_ror:4
-  v += dpp_f32<0x128>(v);             // row_ror:8
+  v += dpp_mov<0xB1>(odd ? sa : sb);  // quad_perm [1,0,3,2]: partner's value of my quarter
+  v += dpp_mov<0x4E>(v);              // quad_perm [2,3,0,1]
+  v += dpp_mov<0x124>(v);             // row_ror:4
+  v += dpp_mov<0x128>(v);             // row_ror:8
   return v;
 }
 

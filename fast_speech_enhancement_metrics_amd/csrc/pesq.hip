@@ -36,8 +36,6 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <atomic>
-#include <mutex>
 #include <type_traits>
 
 #include "fsem_fft.h"
@@ -128,16 +126,12 @@ __device__ __forceinline__ int range_shift(float peak) {
 
 // Wave maximum of non-negative floats (as integers: same order), uniform result: DPP row
 // rotations, then row broadcasts (rows outside the mask read 0, the identity); lane 63 holds it.
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_rot(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, false);
-}
 __device__ __forceinline__ float wave_max_pos(float v) {
   uint32_t e = __float_as_uint(v);
-  e = max(e, dpp_rot<0x121>(e));  // row_ror:1
-  e = max(e, dpp_rot<0x122>(e));  // row_ror:2
-  e = max(e, dpp_rot<0x124>(e));  // row_ror:4
-  e = max(e, dpp_rot<0x128>(e));  // row_ror:8
+  e = max(e, dpp_mov<0x121>(e));  // row_ror:1
+  e = max(e, dpp_mov<0x122>(e));  // row_ror:2
+  e = max(e, dpp_mov<0x124>(e));  // row_ror:4
+  e = max(e, dpp_mov<0x128>(e));  // row_ror:8
   e = max(e, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e, 0x142, 0xA, 0xF, false));  // row_bcast:15
   e = max(e, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e, 0x143, 0xC, 0xF, false));  // row_bcast:31
   return __uint_as_float(__builtin_amdgcn_readlane(e, 63));
@@ -1228,33 +1222,22 @@ extern "C" int fsem_debug_read_stamps(void *dst, size_t bytes) {
 }
 #endif
 
-// range bookkeeping after the partials: pexp [2B nseg], count, item queue, flags [2B], worklist [2B] (int)
-static size_t front_rng_ints(int64_t batch, int64_t length) {
-  return (size_t)(2 * batch) * (size_t)pesq::geometry(length).nseg + 2 + 4 * (size_t)batch;
-}
-
 extern "C" size_t fsem_pesq_front_workspace_bytes(int64_t batch, int64_t length) {
-  return pesq::front_ppart_bytes(batch, length) + align_up(sizeof(int) * front_rng_ints(batch, length), 256);
+  return layout_bytes(pesq::front_layout, batch, length);
 }
 
 extern "C" size_t fsem_pesq_workspace_bytes(int64_t batch, int64_t length) {
-  const pesq::Geometry g = pesq::geometry(length);
-  size_t bytes = fsem_pesq_front_workspace_bytes(batch, length);
-  bytes += align_up(sizeof(float) * (size_t)(2 * batch) * pesq::NBARK * (size_t)pesq::bark_ld(g.F), 256);  // bark
-  bytes += align_up(sizeof(float) * (size_t)(2 * batch), 256);                               // power
-  bytes += fsem_pesq_back_workspace_bytes(batch, length);                                     // back
-  return bytes;
+  return layout_bytes(pesq::wb_layout, batch, length);
 }
 
 int fsem::pesq::launch_front(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
-                             const int32_t *lengths, float *bark, float *power, void *ws, size_t ws_bytes,
-                             float *y10, int64_t y_ld, float2 *vad, int64_t v_ld, hipStream_t st,
-                             bool power_sums) {
+                             const int32_t *lengths, float *bark, float *power, const FrontWs &fw, float *y10,
+                             int64_t y_ld, float2 *vad, int64_t v_ld, hipStream_t st, bool power_sums) {
   if (!ref || !deg || !bark || (power_sums && !power) || batch <= 0 || length <= 0 || ld < length || length > kMaxLength)
     return FSEM_EINVAL;
   const pesq::Geometry g = pesq::geometry(length);
   if (g.F < 20 && !lengths) return FSEM_ESHORT;
-  if (ws_bytes < fsem_pesq_front_workspace_bytes(batch, length) || !ws) return FSEM_EWORKSPACE;
+  if (!fw.ppart || !fw.rng) return FSEM_EWORKSPACE;
   const int64_t nitems = 2 * batch * (int64_t)g.nseg;
   const int ncu = cu_count();
   // 2 resident workgroups per CU; FSEM_FRONT_WGS_PER_CU (diagnostics only) overrides
@@ -1271,9 +1254,8 @@ int fsem::pesq::launch_front(const float *ref, const float *deg, int64_t batch, 
   }();
   const int64_t cus = (front_cus > 0 && front_cus < ncu) ? front_cus : ncu;
   const int64_t grid = std::min<int64_t>(nitems, cus * wgs_per_cu);
-  float *ppart = static_cast<float *>(ws);
-  int *rng = reinterpret_cast<int *>(static_cast<char *>(ws) + pesq::front_ppart_bytes(batch, length));
-  int *pexp = rng;
+  float *ppart = fw.ppart;
+  int *rng = fw.rng, *pexp = fw.rng;  // the range shifts lead the bookkeeping (front_layout)
   // shifts, worklist count, item queue and flags start at zero (the worklist itself is written
   // before read); the size rounded up to 16 bytes (inside the 256-aligned region) so the runtime
   // fills it with one kernel instead of an aligned body and a tail
@@ -1308,11 +1290,18 @@ int fsem::pesq::launch_front(const float *ref, const float *deg, int64_t batch, 
   return FSEM_OK;
 }
 
+// the front workspace laid out over ws, or nulls when it does not fit (launch_front reports it)
+static pesq::FrontWs front_ws(void *ws, size_t ws_bytes, int64_t batch, int64_t length) {
+  Arena a(ws);
+  const pesq::FrontWs fw = pesq::front_layout(a, batch, length);
+  return a.fits(ws_bytes) ? fw : pesq::FrontWs{};
+}
+
 extern "C" int fsem_pesq_front_f32(const float *ref, const float *deg, int64_t batch, int64_t length,
                                    int64_t ld, const int32_t *lengths, float *bark, float *power, void *ws,
                                    size_t ws_bytes, void *stream) {
-  return pesq::launch_front(ref, deg, batch, length, ld, lengths, bark, power, ws, ws_bytes, nullptr, 0, nullptr,
-                            0, (hipStream_t)stream);
+  return pesq::launch_front(ref, deg, batch, length, ld, lengths, bark, power, front_ws(ws, ws_bytes, batch, length),
+                            nullptr, 0, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" int fsem_pesq_front_y10_f32(const float *ref, const float *deg, int64_t batch, int64_t length,
@@ -1321,148 +1310,37 @@ extern "C" int fsem_pesq_front_y10_f32(const float *ref, const float *deg, int64
                                        void *stream) {
   if (!y10 || y_ld < (5 * length + 7) / 8 || (y_ld & 3)) return FSEM_EINVAL;
   if (vad && vad_ld < fsem::vad_ld((5 * length + 7) / 8)) return FSEM_EINVAL;
-  return pesq::launch_front(ref, deg, batch, length, ld, lengths, bark, power, ws, ws_bytes, y10, y_ld,
-                            reinterpret_cast<float2 *>(vad), vad_ld, (hipStream_t)stream);
+  return pesq::launch_front(ref, deg, batch, length, ld, lengths, bark, power, front_ws(ws, ws_bytes, batch, length),
+                            y10, y_ld, reinterpret_cast<float2 *>(vad), vad_ld, (hipStream_t)stream);
 }
 
-hipStream_t fsem::side_stream(hipStream_t st) {
-  constexpr int kMaxDev = 64;
-  static std::mutex mu;
-  static hipStream_t side[kMaxDev] = {};
-  int cur = 0;
-  hipDevice_t dev = 0;
-  if (hipGetDevice(&cur) != hipSuccess || hipStreamGetDevice(st, &dev) != hipSuccess) return st;
-  // created on the current device only; a stream of another device keeps its work on one stream
-  if (dev != cur || dev < 0 || dev >= kMaxDev) return st;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!side[dev] && hipStreamCreateWithFlags(&side[dev], hipStreamNonBlocking) != hipSuccess) {
-    side[dev] = nullptr;
-    return st;
-  }
-  return side[dev];
-}
-
-namespace {
-// The join events of one host thread, one per device, released when the thread exits
-// (errors ignored: at process exit the runtime may already be gone).
-struct ThreadEvents {
-  static constexpr int kMaxDev = 64;
-  hipEvent_t ev[kMaxDev] = {};
-  ~ThreadEvents() {
-    for (hipEvent_t &e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-}  // namespace
-
-int fsem::stream_wait(hipStream_t waiter, hipStream_t producer) {
-  if (waiter == producer) return FSEM_OK;
-  // One event per (host thread, device), recorded anew for every edge.  This relies on the
-  // HIP (as CUDA) snapshot semantics of hipStreamWaitEvent: a wait waits for the record that is
-  // the event's most recent one WHEN THE WAIT IS ENQUEUED, so re-recording the event for the
-  // next edge (possibly on another stream) does not move an earlier wait.  No other thread
-  // records this event.
-  thread_local ThreadEvents tev;
-  hipEvent_t *ev = tev.ev;
-  hipDevice_t dev = 0;
-  if (hipStreamGetDevice(producer, &dev) != hipSuccess || dev < 0 || dev >= ThreadEvents::kMaxDev) return FSEM_ELAUNCH;
-  if (!ev[dev]) {
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return FSEM_ELAUNCH;
-    if (cur != dev && hipSetDevice(dev) != hipSuccess) return FSEM_ELAUNCH;
-    const bool made = hipEventCreateWithFlags(&ev[dev], hipEventDisableTiming) == hipSuccess;
-    if (cur != dev) (void)hipSetDevice(cur);
-    if (!made) {
-      ev[dev] = nullptr;
-      return FSEM_ELAUNCH;
-    }
-  }
-  const bool ok = hipEventRecord(ev[dev], producer) == hipSuccess && hipStreamWaitEvent(waiter, ev[dev], 0) == hipSuccess;
-  return ok ? FSEM_OK : FSEM_ELAUNCH;
-}
-
-int fsem::cu_count() {
-  constexpr int kMaxDev = 64;
-  static std::atomic<int> cache[kMaxDev];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 256;
-  int n = cache[dev].load(std::memory_order_relaxed);
-  if (n > 0) return n;
-  n = 256;
-  (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-  cache[dev].store(n, std::memory_order_relaxed);
-  return n;
-}
-
-// Workspace of the whole-metric entry: [front partials | bark | power | back scratch].
-struct WbWs {
-  size_t front;
-  float *bark, *power;
-  char *back;
-};
-static WbWs carve_wb(void *ws, int64_t batch, int64_t length) {
-  const pesq::Geometry g = pesq::geometry(length);
-  WbWs w;
-  char *p = static_cast<char *>(ws);
-  w.front = fsem_pesq_front_workspace_bytes(batch, length);
-  w.bark = reinterpret_cast<float *>(p + w.front);
-  p += w.front + align_up(sizeof(float) * (size_t)(2 * batch) * pesq::NBARK * (size_t)pesq::bark_ld(g.F), 256);
-  w.power = reinterpret_cast<float *>(p);
-  p += align_up(sizeof(float) * (size_t)(2 * batch), 256);
-  w.back = p;
-  return w;
-}
-
-int fsem::pesq::run_wb_front(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
-                             const int32_t *lengths, void *ws, size_t ws_bytes, float *y10, int64_t y_ld,
-                             float2 *vad, int64_t v_ld, hipStream_t stream) {
-  if (!ref || !deg || batch <= 0 || length <= 0 || ld < length || length > kMaxLength) return FSEM_EINVAL;
-  const pesq::Geometry g = pesq::geometry(length);
-  if (g.F < 20 && !lengths) return FSEM_ESHORT;
-  if (!ws || ws_bytes < fsem_pesq_workspace_bytes(batch, length)) return FSEM_EWORKSPACE;
-  const WbWs w = carve_wb(ws, batch, length);
-  return pesq::launch_front(ref, deg, batch, length, ld, lengths, w.bark, w.power, ws, w.front, y10, y_ld, vad,
-                            v_ld, stream, /*power_sums=*/false);
-}
-
-int fsem::pesq::run_wb_back(int64_t batch, int64_t length, const int32_t *lengths, float *mos, void *ws,
-                            hipStream_t back_st) {
-  if (!mos) return FSEM_EINVAL;
-  const WbWs w = carve_wb(ws, batch, length);
-  // the front end's per-segment power partials sit at the start of the workspace (launch_front)
-  return pesq::launch_back(w.bark, nullptr, static_cast<const float *>(ws), batch, length, lengths, mos, w.back,
-                           fsem_pesq_back_workspace_bytes(batch, length), back_st);
-}
-
-int fsem::pesq::run_wb(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
-                       const int32_t *lengths, float *mos, void *ws, size_t ws_bytes, float *y10, int64_t y_ld,
-                       float2 *vad, int64_t v_ld, hipStream_t stream, hipStream_t back_st) {
-  if (!mos) return FSEM_EINVAL;
-  int rc = run_wb_front(ref, deg, batch, length, ld, lengths, ws, ws_bytes, y10, y_ld, vad, v_ld, stream);
+// The whole-metric path: the front end with its range handling (no host-side row scaling, which
+// the stage entries need), then the back end on the same stream; with dist / frames the back
+// end's distances and per-frame disturbances beside the scores.
+static int run_wb(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                  const int32_t *lengths, float *mos, float *dist, float *frames, void *ws, size_t ws_bytes,
+                  hipStream_t st) {
+  if (!mos || !ref || !deg || batch <= 0 || length <= 0 || ld < length || length > kMaxLength) return FSEM_EINVAL;
+  if (pesq::geometry(length).F < 20 && !lengths) return FSEM_ESHORT;
+  Arena a(ws);
+  const pesq::WbWs w = pesq::wb_layout(a, batch, length);
+  if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
+  const int rc = pesq::launch_front(ref, deg, batch, length, ld, lengths, w.bark, w.power, w.front, nullptr, 0,
+                                    nullptr, 0, st, /*power_sums=*/false);
   if (rc != FSEM_OK) return rc;
-  rc = stream_wait(back_st, stream);
-  if (rc != FSEM_OK) return rc;
-  return run_wb_back(batch, length, lengths, mos, ws, back_st);
+  return pesq::launch_back(w.bark, nullptr, &w.front, batch, length, lengths, mos, w.back, st, dist, frames);
 }
 
 extern "C" int fsem_pesq_wb_f32(const float *ref, const float *deg, int64_t batch, int64_t length,
                                 int64_t ld, const int32_t *lengths, float *mos, void *ws, size_t ws_bytes,
                                 void *stream) {
-  return pesq::run_wb(ref, deg, batch, length, ld, lengths, mos, ws, ws_bytes, nullptr, 0, nullptr, 0,
-                       (hipStream_t)stream, (hipStream_t)stream);
+  return run_wb(ref, deg, batch, length, ld, lengths, mos, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream);
 }
 
-// The whole-metric path with the back end's intermediates (ABI 10): the front end with its range
-// handling (no host-side row scaling, which the stage entries need), then the back end's
-// distances and per-frame disturbances beside the scores.
+// (ABI 10)
 extern "C" int fsem_pesq_wb_frames_f32(const float *ref, const float *deg, int64_t batch, int64_t length,
                                        int64_t ld, const int32_t *lengths, float *mos, float *dist, float *frames,
                                        void *ws, size_t ws_bytes, void *stream) {
-  if (!mos || !dist || !frames) return FSEM_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = pesq::run_wb_front(ref, deg, batch, length, ld, lengths, ws, ws_bytes, nullptr, 0, nullptr, 0, st);
-  if (rc != FSEM_OK) return rc;
-  const WbWs w = carve_wb(ws, batch, length);
-  return pesq::launch_back(w.bark, nullptr, static_cast<const float *>(ws), batch, length, lengths, mos, w.back,
-                           fsem_pesq_back_workspace_bytes(batch, length), st, dist, frames);
+  if (!dist || !frames) return FSEM_EINVAL;
+  return run_wb(ref, deg, batch, length, ld, lengths, mos, dist, frames, ws, ws_bytes, (hipStream_t)stream);
 }

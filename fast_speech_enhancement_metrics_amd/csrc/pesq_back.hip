@@ -350,24 +350,20 @@ int fsem::pesq::back_waves(int64_t batch, int64_t length) {
 }
 
 extern "C" size_t fsem_pesq_back_workspace_bytes(int64_t batch, int64_t length) {
-  const pesq::Geometry g = pesq::geometry(length);
-  return align_up(sizeof(float) * (size_t)batch * (size_t)g.F * 4, 256);
+  return layout_bytes(pesq::back_layout, batch, length);
 }
 
-int fsem::pesq::launch_back(const float *bark, const float *power, const float *ppart, int64_t batch,
-                            int64_t length, const int32_t *lengths, float *mos, void *ws, size_t ws_bytes,
-                            hipStream_t stream, float *dist, float *frames) {
-  if (!bark || (!power && !ppart) || !mos || batch <= 0 || length <= 0 || length > kMaxLength) return FSEM_EINVAL;
+int fsem::pesq::launch_back(const float *bark, const float *power, const FrontWs *front, int64_t batch,
+                            int64_t length, const int32_t *lengths, float *mos, float *scratch, hipStream_t stream,
+                            float *dist, float *frames) {
+  if (!bark || (!power && !front) || !mos || batch <= 0 || length <= 0 || length > kMaxLength) return FSEM_EINVAL;
   const pesq::Geometry g = pesq::geometry(length);
   if (g.F < 20 && !lengths) return FSEM_ESHORT;
-  if (!ws || ws_bytes < fsem_pesq_back_workspace_bytes(batch, length)) return FSEM_EWORKSPACE;
+  if (!scratch) return FSEM_EWORKSPACE;
   if (batch > 0x7fffffff) return FSEM_EINVAL;
   const int bw = pesq::back_waves(batch, length);
-  float *scratch = static_cast<float *>(ws);
-  // with the front end's partials, its range shifts follow them (fsem_pesq_front_workspace_bytes)
-  const int *pexp = ppart ? reinterpret_cast<const int *>(reinterpret_cast<const char *>(ppart) +
-                                                          pesq::front_ppart_bytes(batch, length))
-                          : nullptr;
+  const float *ppart = front ? front->ppart : nullptr;
+  const int *pexp = front ? front->rng : nullptr;  // the range shifts lead the bookkeeping (front_layout)
 #define FSEM_BACK(W, S, LDS)                                                                                   \
   hipLaunchKernelGGL((pesq::pesq_back<W, S>), dim3((unsigned)batch), dim3(64 * W), LDS, stream, bark, power, ppart, \
                      pexp, g.nseg, batch, length, lengths, g.F, scratch, mos, dist, frames)
@@ -389,22 +385,34 @@ extern "C" int fsem_pesq_back_f32(const float *bark, const float *power, int64_t
                                   const int32_t *lengths, float *mos, void *ws, size_t ws_bytes,
                                   void *stream) {
   if (!power) return FSEM_EINVAL;
-  return pesq::launch_back(bark, power, nullptr, batch, length, lengths, mos, ws, ws_bytes, (hipStream_t)stream);
+  Arena a(ws);
+  float *scratch = pesq::back_layout(a, batch, length);
+  if (!a.fits(ws_bytes)) scratch = nullptr;
+  return pesq::launch_back(bark, power, nullptr, batch, length, lengths, mos, scratch, (hipStream_t)stream);
+}
+
+// Distances entry: the back end's scratch rows, then the scores it also writes.
+struct DistWs {
+  float *scratch, *mos;
+};
+static DistWs dist_layout(Arena &a, int64_t batch, int64_t length) {
+  DistWs w;
+  w.scratch = pesq::back_layout(a, batch, length);
+  w.mos = a.take<float>((size_t)batch);
+  return w;
 }
 
 extern "C" size_t fsem_pesq_distances_workspace_bytes(int64_t batch, int64_t length) {
-  // the back end's scratch rows, then the scores it also writes
-  return fsem_pesq_back_workspace_bytes(batch, length) + align_up(sizeof(float) * (size_t)batch, 256);
+  return layout_bytes(dist_layout, batch, length);
 }
 
 extern "C" int fsem_pesq_distances_f32(const float *bark, const float *power, int64_t batch, int64_t length,
                                        const int32_t *lengths, float *dist, float *frames, void *ws,
                                        size_t ws_bytes, void *stream) {
   if (!power || !dist || batch <= 0 || length <= 0) return FSEM_EINVAL;
-  if (!ws || ws_bytes < fsem_pesq_distances_workspace_bytes(batch, length)) return FSEM_EWORKSPACE;
-  const size_t back = fsem_pesq_back_workspace_bytes(batch, length);
-  float *mos = reinterpret_cast<float *>(static_cast<char *>(ws) + back);
-  return pesq::launch_back(bark, power, nullptr, batch, length, lengths, mos, ws, back, (hipStream_t)stream, dist,
+  Arena a(ws);
+  const DistWs w = dist_layout(a, batch, length);
+  if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
+  return pesq::launch_back(bark, power, nullptr, batch, length, lengths, w.mos, w.scratch, (hipStream_t)stream, dist,
                            frames);
 }
-

@@ -60,7 +60,6 @@ struct Part {
 };
 static_assert(sizeof(Part) == 128, "one record is 128 bytes");
 
-inline size_t window_bytes(const Geo &g) { return align_up((size_t)g.win * sizeof(float), 256); }
 inline int64_t chunks(int64_t length, const Geo &g) { return (length + g.C - 1) / g.C; }
 inline size_t lds_bytes(const Geo &g) {
   return 4 * 7 * sizeof(double) + (size_t)g.K * 8 * sizeof(float) + (size_t)(g.win + 8) * sizeof(float);
@@ -77,10 +76,6 @@ __global__ void sdr_window(float *__restrict__ w2, int win) {
 __device__ __forceinline__ float frame_db(float S, float D) {
   const float v = 10.f * log10f(S / (D + 1e-10f) + 1e-10f);
   return fminf(fmaxf(v, -10.f), 35.f);
-}
-
-__device__ __forceinline__ int row_length(const int32_t *__restrict__ lengths, int64_t row, int length) {
-  return lengths ? min(max(lengths[row], 0), length) : length;
 }
 
 template <bool VEC>
@@ -258,6 +253,18 @@ __global__ __launch_bounds__(FT) void sdr_finish(const Part *__restrict__ part, 
   si_out[b] = si;
 }
 
+// Workspace: the squared window, then one record per (row, chunk).
+struct Ws {
+  float *w2;
+  Part *part;
+};
+inline Ws layout(Arena &a, int64_t batch, int64_t length, const Geo &g) {
+  Ws w;
+  w.w2 = a.take<float>((size_t)g.win);
+  w.part = a.take<Part>((size_t)batch * (size_t)chunks(length, g));
+  return w;
+}
+
 }  // namespace sdr
 }  // namespace fsem
 
@@ -282,7 +289,7 @@ extern "C" int64_t fsem_sdr_chunk(int32_t sample_rate) {
 extern "C" size_t fsem_sdr_workspace_bytes(int64_t batch, int64_t length, int32_t sample_rate) {
   sdr::Geo g;
   if (!sdr::make_geo(sample_rate, &g) || batch < 1 || length < 1 || length > kMaxLength) return 0;
-  return sdr::window_bytes(g) + (size_t)batch * (size_t)sdr::chunks(length, g) * sizeof(sdr::Part);
+  return layout_bytes(sdr::layout, batch, length, g);
 }
 
 extern "C" int fsem_sdr_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
@@ -292,27 +299,27 @@ extern "C" int fsem_sdr_f32(const float *ref, const float *deg, int64_t batch, i
     return FSEM_EINVAL;
   sdr::Geo g;
   if (!sdr::make_geo(sample_rate, &g)) return FSEM_ERATE;
-  if (!ws || ws_bytes < fsem_sdr_workspace_bytes(batch, length, sample_rate)) return FSEM_EWORKSPACE;
+  Arena a(ws);
+  const sdr::Ws w = sdr::layout(a, batch, length, g);
+  if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  float *w2 = static_cast<float *>(ws);
-  sdr::Part *part = reinterpret_cast<sdr::Part *>(static_cast<char *>(ws) + sdr::window_bytes(g));
   const int nchunk = (int)sdr::chunks(length, g);
-  hipLaunchKernelGGL(sdr::sdr_window, dim3((unsigned)((g.win + 255) / 256)), dim3(256), 0, st, w2, g.win);
+  hipLaunchKernelGGL(sdr::sdr_window, dim3((unsigned)((g.win + 255) / 256)), dim3(256), 0, st, w.w2, g.win);
   FSEM_CHECK_LAUNCH();
   // 16-byte loads where every row of both operands starts on a 16-byte boundary
   const bool vec = (((uintptr_t)ref | (uintptr_t)deg) & 15) == 0 && ld % 4 == 0;
   const size_t lds = sdr::lds_bytes(g);
   for (int64_t r0 = 0; r0 < batch; r0 += kMaxGridY) {
-    const dim3 grid((unsigned)nchunk, (unsigned)std::min(batch - r0, kMaxGridY));
+    const dim3 grid = grid_slice((unsigned)nchunk, batch, r0);
     if (vec)
       hipLaunchKernelGGL(sdr::sdr_partial<true>, grid, dim3(sdr::T), lds, st, ref, deg, ld, lengths, (int)length, r0,
-                         g.hop, g.K, w2, part, nchunk);
+                         g.hop, g.K, w.w2, w.part, nchunk);
     else
       hipLaunchKernelGGL(sdr::sdr_partial<false>, grid, dim3(sdr::T), lds, st, ref, deg, ld, lengths, (int)length, r0,
-                         g.hop, g.K, w2, part, nchunk);
+                         g.hop, g.K, w.w2, w.part, nchunk);
     FSEM_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(sdr::sdr_finish, dim3((unsigned)((batch + sdr::FT - 1) / sdr::FT)), dim3(sdr::FT), 0, st, part,
+  hipLaunchKernelGGL(sdr::sdr_finish, dim3((unsigned)((batch + sdr::FT - 1) / sdr::FT)), dim3(sdr::FT), 0, st, w.part,
                      nchunk, lengths, (int)length, batch, g.hop, g.K, zero_mean, si_sdr, snr, seg_snr);
   FSEM_CHECK_LAUNCH();
   return FSEM_OK;

@@ -306,10 +306,6 @@ __device__ unsigned long long g_tob_stamps[kTobStampBlocks][4];
 // denormal), packed (clean << 16 | denoised): per-lane maxima, then a DPP reduction (row
 // rotations, row broadcasts) with a packed 16-bit max -- both signals per instruction, no LDS --
 // whose last lane holds the wave's maxima (uniform result).
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, false);
-}
 __device__ __forceinline__ uint32_t peak_exponents(float c0, float c1, float c2, float c3, float d0, float d1,
                                                    float d2, float d3) {
   typedef unsigned short us2 __attribute__((ext_vector_type(2)));
@@ -323,10 +319,10 @@ __device__ __forceinline__ uint32_t peak_exponents(float c0, float c1, float c2,
   auto pmax = [](uint32_t x, uint32_t y) {
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2, x), __builtin_bit_cast(us2, y)));
   };
-  e = pmax(e, dpp_u<0x121>(e));  // row_ror:1
-  e = pmax(e, dpp_u<0x122>(e));  // row_ror:2
-  e = pmax(e, dpp_u<0x124>(e));  // row_ror:4
-  e = pmax(e, dpp_u<0x128>(e));  // row_ror:8 -> every lane holds its row's maxima
+  e = pmax(e, dpp_mov<0x121>(e));  // row_ror:1
+  e = pmax(e, dpp_mov<0x122>(e));  // row_ror:2
+  e = pmax(e, dpp_mov<0x124>(e));  // row_ror:4
+  e = pmax(e, dpp_mov<0x128>(e));  // row_ror:8 -> every lane holds its row's maxima
   // rows 1 and 3 take rows 0 and 2 (row_bcast:15), rows 2 and 3 take lane 31 (row_bcast:31);
   // rows outside the mask read 0, the identity of the max
   e = pmax(e, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e, 0x142, 0xA, 0xF, false));
@@ -782,39 +778,22 @@ inline int make_geometry(int64_t length, int32_t sr, Geometry *g, ResampleKernel
   return FSEM_OK;
 }
 
-inline size_t ws_bytes(int64_t B, const Geometry &g) {
-  size_t s = 0;
-  s += align_up(sizeof(float2) * (size_t)B * (size_t)g.v_ld, 256);        // VAD quarter sums
-  s += align_up(sizeof(int) * (size_t)B * g.nv_ld, 256);                  // kept indices
-  s += align_up(sizeof(int) * (size_t)B, 256);                            // kept counts
-  s += align_up(sizeof(float) * (size_t)(2 * B) * NB * (size_t)g.tmax, 256);  // tob
-  s += align_up(sizeof(double) * 2 * (size_t)B * (size_t)seg_blocks(g.tmax), 256);  // segment block sums
-  s += align_up(sizeof(float) * (size_t)(2 * B) * (size_t)g.y_ld, 256);      // 10 kHz signals
-  return s;
-}
-
-// Pointers into a STOI workspace laid out by ws_bytes().
+// The STOI workspace (Arena, fsem_common.h).
 struct Ws {
   float2 *vad;
   int *idx, *kept;
-  float *tob, *y10;
+  float *tob;
   double *part;
+  float *y10;
 };
-
-inline Ws carve(void *ws, int64_t B, const Geometry &g) {
+inline Ws layout(Arena &a, int64_t B, const Geometry &g) {
   Ws w;
-  char *p = static_cast<char *>(ws);
-  w.vad = reinterpret_cast<float2 *>(p);
-  p += align_up(sizeof(float2) * (size_t)B * (size_t)g.v_ld, 256);
-  w.idx = reinterpret_cast<int *>(p);
-  p += align_up(sizeof(int) * (size_t)B * g.nv_ld, 256);
-  w.kept = reinterpret_cast<int *>(p);
-  p += align_up(sizeof(int) * (size_t)B, 256);
-  w.tob = reinterpret_cast<float *>(p);
-  p += align_up(sizeof(float) * (size_t)(2 * B) * NB * (size_t)g.tmax, 256);
-  w.part = reinterpret_cast<double *>(p);
-  w.y10 = reinterpret_cast<float *>(static_cast<char *>(ws) + ws_bytes(B, g) -
-                                    align_up(sizeof(float) * (size_t)(2 * B) * (size_t)g.y_ld, 256));
+  w.vad = a.take<float2>((size_t)B * (size_t)g.v_ld);                 // VAD quarter sums
+  w.idx = a.take<int>((size_t)B * g.nv_ld);                           // kept indices
+  w.kept = a.take<int>((size_t)B);                                    // kept counts
+  w.tob = a.take<float>((size_t)(2 * B) * NB * (size_t)g.tmax);       // tob
+  w.part = a.take<double>(2 * (size_t)B * (size_t)seg_blocks(g.tmax));  // segment block sums
+  w.y10 = a.take<float>((size_t)(2 * B) * (size_t)g.y_ld);            // 10 kHz signals
   return w;
 }
 
@@ -823,8 +802,8 @@ inline int run_seg(int64_t B, const float *tob, int64_t tmax, const int *kept, d
                    float *estoi_out, hipStream_t st) {
   const int P = seg_blocks(tmax);
   for (int64_t b0 = 0; b0 < B; b0 += kMaxGridY) {
-    hipLaunchKernelGGL(stoi_seg, dim3((unsigned)P, (unsigned)std::min(B - b0, kMaxGridY)), dim3(SEG_T), 0, st, tob,
-                       B, tmax, kept, part, P, b0);
+    hipLaunchKernelGGL(stoi_seg, grid_slice((unsigned)P, B, b0), dim3(SEG_T), 0, st, tob, B, tmax, kept, part, P,
+                       b0);
     FSEM_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(stoi_seg_sum, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, part, P, B, kept, stoi_out,
@@ -839,8 +818,8 @@ inline int run_tail(int64_t B, const Geometry &g, const Rows &rows, const float 
   hipLaunchKernelGGL(stoi_select, dim3((unsigned)B), dim3(256), 0, st, vad, g.v_ld, g.nv_ld, rows, idx, kept);
   FSEM_CHECK_LAUNCH();
   for (int64_t b0 = 0; b0 < B; b0 += kMaxGridY) {
-    hipLaunchKernelGGL(stoi_tob, dim3((unsigned)((g.tmax + TF - 1) / TF), (unsigned)std::min(B - b0, kMaxGridY)),
-                       dim3(64 * TOB_WAVES), 0, st, y10, g.y_ld, B, rows, idx, kept, g.nv_ld, tob, tmax, b0);
+    hipLaunchKernelGGL(stoi_tob, grid_slice((unsigned)((g.tmax + TF - 1) / TF), B, b0), dim3(64 * TOB_WAVES), 0, st,
+                       y10, g.y_ld, B, rows, idx, kept, g.nv_ld, tob, tmax, b0);
     FSEM_CHECK_LAUNCH();
   }
   if (stoi_out) return run_seg(B, tob, tmax, kept, part, stoi_out, estoi_out, st);
@@ -856,8 +835,9 @@ inline int run(const float *ref, const float *deg, int64_t B, int64_t length, in
   if (rc != FSEM_OK) return rc;
   if (g.NV <= 0 && !lengths) return FSEM_ESHORT;  // with lengths: NaN rows instead
   const Rows rows{lengths, length, rk.orig, rk.nw};
-  if (!ws || ws_size < ws_bytes(B, g)) return FSEM_EWORKSPACE;
-  Ws w = carve(ws, B, g);
+  Arena a(ws);
+  Ws w = layout(a, B, g);
+  if (!a.fits(ws_size)) return FSEM_EWORKSPACE;
   int64_t tmax = g.tmax;
   if (tob_out) {
     w.tob = tob_out;
@@ -878,14 +858,13 @@ inline int run(const float *ref, const float *deg, int64_t B, int64_t length, in
     rc = launch_resample_tiled(deg, B, length, ld, lengths, w.y10 + g.y_ld, 2 * g.y_ld, 0, rk, st);
     if (rc != FSEM_OK) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += kMaxGridY) {
-      hipLaunchKernelGGL(stoi_vad10, dim3((unsigned)((g.L10 + VQ - 1) / VQ), (unsigned)std::min(B - b0, kMaxGridY)),
-                         dim3(256), 0, st, w.y10, g.y_ld, rows, w.vad, g.v_ld, b0);
+      hipLaunchKernelGGL(stoi_vad10, grid_slice((unsigned)((g.L10 + VQ - 1) / VQ), B, b0), dim3(256), 0, st, w.y10,
+                         g.y_ld, rows, w.vad, g.v_ld, b0);
       FSEM_CHECK_LAUNCH();
     }
   } else {
     for (int64_t b0 = 0; b0 < B; b0 += kMaxGridY) {
-      hipLaunchKernelGGL(stoi_resample_vad,
-                         dim3((unsigned)((g.L10 + VF3 * 128 - 1) / (VF3 * 128)), (unsigned)std::min(B - b0, kMaxGridY)),
+      hipLaunchKernelGGL(stoi_resample_vad, grid_slice((unsigned)((g.L10 + VF3 * 128 - 1) / (VF3 * 128)), B, b0),
                          dim3(256), 0, st, ref, deg, rows, ld, g.mode, rk, w.y10, g.y_ld, w.vad, g.v_ld, b0);
       FSEM_CHECK_LAUNCH();
     }
@@ -903,7 +882,7 @@ extern "C" size_t fsem_stoi_workspace_bytes(int64_t batch, int64_t length, int32
   stoi::Geometry g;
   ResampleKernel rk;
   if (stoi::make_geometry(length, sample_rate, &g, &rk) != FSEM_OK) return 0;
-  return stoi::ws_bytes(batch, g);
+  return layout_bytes(stoi::layout, batch, g);
 }
 
 extern "C" int fsem_stoi_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
@@ -929,8 +908,23 @@ extern "C" int fsem_stoi_tob_f32(const float *ref10, const float *deg10, int64_t
                    ws_bytes, (hipStream_t)stream);
 }
 
+// Joint entry: the whole-metric PESQ layout, then the STOI layout, on one arena.
+struct JointWs {
+  pesq::WbWs pesq;
+  stoi::Ws stoi;
+};
+static JointWs joint_layout(Arena &a, int64_t batch, int64_t length, const stoi::Geometry &g) {
+  JointWs w;
+  w.pesq = pesq::wb_layout(a, batch, length);
+  w.stoi = stoi::layout(a, batch, g);
+  return w;
+}
+
 extern "C" size_t fsem_pesq_stoi_workspace_bytes(int64_t batch, int64_t length) {
-  return align_up(fsem_pesq_workspace_bytes(batch, length), 256) + fsem_stoi_workspace_bytes(batch, length, 16000);
+  stoi::Geometry g;
+  ResampleKernel rk;
+  if (stoi::make_geometry(length, 16000, &g, &rk) != FSEM_OK) return 0;  // (16 -> 10 kHz always has a kernel)
+  return layout_bytes(joint_layout, batch, length, g);
 }
 
 extern "C" int fsem_pesq_stoi_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
@@ -944,9 +938,11 @@ extern "C" int fsem_pesq_stoi_f32(const float *ref, const float *deg, int64_t ba
   int rc = stoi::make_geometry(length, 16000, &g, &rk);
   if (rc != FSEM_OK) return rc;
   if (!lengths && (g.NV <= 0 || fsem_pesq_frames(length) < 20)) return FSEM_ESHORT;
-  if (!ws || ws_bytes < fsem_pesq_stoi_workspace_bytes(batch, length)) return FSEM_EWORKSPACE;
-  const size_t pesq_bytes = align_up(fsem_pesq_workspace_bytes(batch, length), 256);
-  stoi::Ws w = stoi::carve(static_cast<char *>(ws) + pesq_bytes, batch, g);
+  Arena a(ws);
+  const JointWs jw = joint_layout(a, batch, length, g);
+  if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
+  const pesq::WbWs &p = jw.pesq;
+  const stoi::Ws &w = jw.stoi;
   const stoi::Rows rows{lengths, length, rk.orig, rk.nw};
   hipStream_t st = (hipStream_t)stream;
   // PESQ-wb with the 10 kHz rows emitted from the same input tiles; the PESQ back end runs on a
@@ -957,12 +953,13 @@ extern "C" int fsem_pesq_stoi_f32(const float *ref, const float *deg, int64_t ba
   // stoi_select / stoi_tob, since neither fills the chip.  Both only read what the front end wrote.
   const hipStream_t side = side_stream(st);
   const bool early = pesq::back_waves(batch, length) > 1;
-  rc = pesq::run_wb_front(ref, deg, batch, length, ld, lengths, ws, pesq_bytes, w.y10, g.y_ld, w.vad, g.v_ld, st);
+  rc = pesq::launch_front(ref, deg, batch, length, ld, lengths, p.bark, p.power, p.front, w.y10, g.y_ld, w.vad,
+                          g.v_ld, st, /*power_sums=*/false);
   if (rc != FSEM_OK) return rc;
   if (early) {
     rc = stream_wait(side, st);
     if (rc != FSEM_OK) return rc;
-    rc = pesq::run_wb_back(batch, length, lengths, mos, ws, side);
+    rc = pesq::launch_back(p.bark, nullptr, &p.front, batch, length, lengths, mos, p.back, side);
     if (rc != FSEM_OK) return rc;
     rc = stoi::run_tail(batch, g, rows, w.y10, w.vad, w.idx, w.kept, w.tob, g.tmax, w.part, stoi_out, estoi_out,
                         st);
@@ -971,7 +968,7 @@ extern "C" int fsem_pesq_stoi_f32(const float *ref, const float *deg, int64_t ba
     if (rc != FSEM_OK) return rc;
     rc = stream_wait(side, st);
     if (rc != FSEM_OK) return rc;
-    rc = pesq::run_wb_back(batch, length, lengths, mos, ws, side);
+    rc = pesq::launch_back(p.bark, nullptr, &p.front, batch, length, lengths, mos, p.back, side);
     if (rc != FSEM_OK) return rc;
     rc = stoi::run_seg(batch, w.tob, g.tmax, w.kept, w.part, stoi_out, estoi_out, st);
   }
@@ -987,43 +984,3 @@ extern "C" int fsem_debug_read_tob_stamps(void *dst, size_t bytes) {
              ? FSEM_OK : FSEM_ELAUNCH;
 }
 #endif
-
-extern "C" const char *fsem_strerror(int code) {
-  switch (code) {
-    case FSEM_OK: return "ok";
-    case FSEM_EINVAL: return "invalid argument";
-    case FSEM_EWORKSPACE: return "workspace too small";
-    case FSEM_ELAUNCH: return "HIP launch failed";
-    case FSEM_ESHORT: return "input too short for the metric";
-    case FSEM_ERATE: return "unsupported sample-rate pair";
-    default: return "unknown error";
-  }
-}
-
-extern "C" int fsem_version(void) { return 11; }  // 11: + fsem_sdr_*; 10: + fsem_pesq_wb_frames_f32; 9: + fsem_pesq_bad_intervals_*, fsem_pesq_pool_f32; 8: + fsem_time_align_p862_*; 7: + fsem_host_buffer_mapped; 6: + fsem_build_id; 5: + fsem_time_align_utt_*; 4: + fsem_pre_emphasize_f32; 3: + fsem_time_align_*, fsem_pesq_distances_*
-
-// The build's content hash (_build.py passes -DFSEM_BUILD_ID); the marker prefix lets the host
-// layer read the id from the file without loading it (_build.library_build_id).
-#ifndef FSEM_BUILD_ID
-#define FSEM_BUILD_ID "unknown"
-#endif
-static const char kBuildIdMarker[] = "FSEM_BUILD_ID:" FSEM_BUILD_ID;
-extern "C" const char *fsem_build_id(void) { return kBuildIdMarker + 14; }
-// The offload target, recorded apart from the content hash (_build.library_build_arch): a library
-// built for another target is refused at load rather than rebuilt.
-#ifndef FSEM_BUILD_ARCH
-#define FSEM_BUILD_ARCH "unknown"
-#endif
-__attribute__((used)) static const char kBuildArchMarker[] = "FSEM_BUILD_ARCH:" FSEM_BUILD_ARCH;
-
-// The drop-in call's scores go straight into its pinned host buffer when the runtime maps that
-// buffer into the device address space at the same address (hipHostMalloc memory on ROCm).
-extern "C" int fsem_host_buffer_mapped(const void *p) {
-  if (!p) return 0;
-  void *d = nullptr;
-  if (hipHostGetDevicePointer(&d, const_cast<void *>(p), 0) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return d == p ? 1 : 0;
-}
