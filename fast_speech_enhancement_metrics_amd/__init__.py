@@ -5,6 +5,7 @@
     STOI(sample_rate=16000, use_gpu=True)(clean, denoised)  -> [{"STOI": ..., "ESTOI": ...}, ...]
     PESQ_STOI(16000, use_gpu=True)(clean, denoised)        -> [{"PESQ", "STOI", "ESTOI"}, ...]  (one pass)
     SDR(sample_rate=16000, use_gpu=True)(clean, denoised)   -> [{"SI-SDR", "SNR", "SegSNR"}, ...]  (extension)
+    Composite(16000, use_gpu=True)(clean, denoised)         -> [{"CSIG", "CBAK", "COVL", "PESQ", "LLR", "WSS", "SegSNR"}, ...]  (extension)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
 """
@@ -13,6 +14,7 @@ from .PESQ import PESQ
 from .STOI import STOI
 from .joint import PESQ_STOI
 from .SDR import SDR
+from .Composite import Composite
 from .alignment import time_align
 
-__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "time_align"]
+__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "time_align"]

@@ -2,7 +2,7 @@
 
     python -m fast_speech_enhancement_metrics_amd._build
 
-Output: fast_speech_enhancement_metrics_amd/lib/libfsem.so (git-ignored, travels with the
+Output: fast_speech_enhancement_metrics_amd/lib/libfsem.so and libfsem_composite.so (git-ignored, travels with the
 repo snapshot to the GPU box).  Cross-compiles without a GPU.
 """
 from __future__ import annotations
@@ -38,6 +38,11 @@ SOURCE_FLAGS = {"pesq.hip": ["-fno-slp-vectorize"], "stoi.hip": _ILP, "resample.
 HEADERS = ["fsem_common.h", "fsem_fft.h", "fsem_internal.h", "fsem_pesq.h", "fsem_resample.h", "fsem_tables.inc",
            "fsem_vad.h"]
 HEADER_ABI = os.path.join(PKG, "..", "include", "fsem.h")
+# the Composite metric's engine: a library of its own that links against libfsem.so (whose entry
+# set is pinned entry by entry); built with it, from the same content hash
+COMPOSITE_LIB = os.path.join(LIBDIR, "libfsem_composite.so")
+COMPOSITE_SOURCES = ["composite.hip"]
+COMPOSITE_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_composite.h")
 ARCH = os.environ.get("FSEM_OFFLOAD_ARCH", "gfx950")
 # code-generation flags; the target (--offload-arch=ARCH) is added at build time and recorded in
 # the library on its own (FSEM_BUILD_ARCH): a library built for another target is refused at
@@ -60,7 +65,7 @@ def _hipcc() -> str:
 
 def deps() -> list:
     """Every file whose content the library depends on."""
-    return [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [HEADER_ABI]
+    return [os.path.join(CSRC, f) for f in SOURCES + HEADERS + COMPOSITE_SOURCES] + [HEADER_ABI, COMPOSITE_HEADER_ABI]
 
 
 def source_hash() -> str:
@@ -103,7 +108,8 @@ def _stale() -> bool:
     """True when libfsem.so is missing or was built from other sources or flags than the tree's
     (content hash: an edited header or a changed SOURCE_FLAGS entry rebuilds; a touched file
     whose content is unchanged does not), or for another target than ARCH."""
-    return library_build_id(LIB) != source_hash() or library_build_arch(LIB) != ARCH
+    want = source_hash()
+    return library_build_id(LIB) != want or library_build_arch(LIB) != ARCH or library_build_id(COMPOSITE_LIB) != want
 
 
 def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> str:
@@ -121,7 +127,7 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
     objs = []
     try:
         procs = []
-        for src in SOURCES:  # one object per source (per-source flags, compiled in parallel), one library
+        for src in SOURCES + ([] if stamps else COMPOSITE_SOURCES):  # one object per source (per-source flags, compiled in parallel), one library
             obj = os.path.join(objdir, src.replace(".hip", ".o"))
             cmd = base + SOURCE_FLAGS.get(src, []) + ["-c", "-o", obj, os.path.join(CSRC, src)]
             if verbose:
@@ -131,12 +137,21 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
         for p, cmd in procs:
             if p.wait() != 0:
                 raise subprocess.CalledProcessError(p.returncode, cmd)
+        cobjs = [] if stamps else objs[len(SOURCES):]
         tmp = f"{lib}.{os.getpid()}.tmp"
-        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + objs
+        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + objs[:len(SOURCES)]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd, cwd=CSRC)
         os.replace(tmp, lib)
+        if cobjs:  # libfsem_composite.so needs libfsem.so, found next to it at load time
+            tmp = f"{COMPOSITE_LIB}.{os.getpid()}.tmp"
+            cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + cobjs + \
+                  [f"-L{LIBDIR}", "-lfsem", "-Wl,-rpath,$ORIGIN"]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd, cwd=CSRC)
+            os.replace(tmp, COMPOSITE_LIB)
     finally:
         shutil.rmtree(objdir, ignore_errors=True)
     return lib

@@ -10,6 +10,7 @@ rows map to 0, rows far below 1e-12 to ~0, as the engine and the oracle).
 """
 from __future__ import annotations
 
+import functools
 import math
 import threading
 
@@ -702,3 +703,145 @@ def sdr(clean: torch.Tensor, noisy: torch.Tensor, sample_rate: int = 16000, zero
         seg = nan.clone()
     bad = ~(torch.isfinite(s).all(1) & torch.isfinite(h).all(1))
     return tuple(torch.where(bad, nan, v) for v in (si, snr, seg))
+
+
+# ----------------------------------------------------------------------------- Composite family
+# CSIG, CBAK, COVL with LLR and WSS (Hu & Loizou 2008; not in the reference; engine:
+# csrc/composite.hip, definitions: include/fsem_composite.h), float64, all frames of a chunk of
+# rows at once.
+_WSS_CENTRE = (50.0, 120.0, 190.0, 260.0, 330.0, 400.0, 470.0, 540.0, 617.372, 703.378, 798.717, 904.128, 1020.38,
+               1148.30, 1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17,
+               3597.63)
+_WSS_WIDTH = (70.0,) * 7 + (77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914, 140.423, 153.823, 168.154, 183.457,
+                            199.776, 217.153, 235.631, 255.255, 276.072, 298.126, 321.465, 346.136)
+_COMPOSITE_ROWS = 8  # rows per vectorised pass (bounds the [rows, F, win] temporaries)
+
+
+def composite_order(sample_rate: int) -> int:
+    """LPC order of the LLR: 10 at 8 kHz, 16 at 16 kHz."""
+    return 10 if int(sample_rate) < 10000 else 16
+
+
+@functools.lru_cache(maxsize=4)
+def _wss_filters(sample_rate: int, nfft: int) -> torch.Tensor:
+    """[25, nfft / 2] float64 critical-band filters."""
+    H = nfft // 2
+    half = sample_rate / 2
+    j = torch.arange(H, dtype=torch.float64)
+    rows = []
+    for c, b in zip(_WSS_CENTRE, _WSS_WIDTH):
+        f0 = math.floor(c * H / half)
+        g = torch.exp(-11.0 * ((j - f0) / (b * H / half)) ** 2 + math.log(_WSS_WIDTH[0]) - math.log(b))
+        rows.append(torch.where(g > math.exp(-30.0 / (2 * 2.303)), g, torch.zeros_like(g)))
+    return torch.stack(rows)
+
+
+def _lpc(R: torch.Tensor, P: int) -> torch.Tensor:
+    """Levinson-Durbin on [..., P + 1] autocorrelations -> prediction-error filters [..., P + 1]."""
+    a = torch.zeros_like(R)
+    a[..., 0] = 1.0
+    E = R[..., 0].clone()
+    for i in range(1, P + 1):
+        acc = R[..., i] + (a[..., 1:i] * R[..., 1:i].flip(-1)).sum(-1)
+        k = -acc / E
+        prev = a[..., 1:i].clone()
+        a[..., 1:i] = prev + k[..., None] * prev.flip(-1)
+        a[..., i] = k
+        E = E * (1 - k * k)
+    return a
+
+
+def _nearest_peaks(e: torch.Tensor) -> torch.Tensor:
+    """[..., 25] band energies -> [..., 24] nearest peaks (the published search, its quirk kept)."""
+    sl = e[..., 1:] - e[..., :-1]
+    nb = sl.shape[-1]
+    up = sl > 0
+    down = sl <= 0
+    # first m >= i that does not rise (24 when every later slope rises)
+    nxt = torch.full(sl.shape, nb, dtype=torch.int64)
+    cur = torch.full(sl.shape[:-1], nb, dtype=torch.int64)
+    for i in range(nb - 1, -1, -1):
+        cur = torch.where(up[..., i], cur, torch.full_like(cur, i))
+        nxt[..., i] = cur
+    # last m <= i that does not fall (-1 when every earlier slope falls)
+    prv = torch.full(sl.shape, -1, dtype=torch.int64)
+    cur = torch.full(sl.shape[:-1], -1, dtype=torch.int64)
+    for i in range(nb):
+        cur = torch.where(down[..., i], cur, torch.full_like(cur, i))
+        prv[..., i] = cur
+    at = torch.where(up, nxt - 1, prv + 1)
+    return torch.gather(e, -1, at)
+
+
+def _trimmed_mean(v: torch.Tensor) -> torch.Tensor:
+    """[B, F] -> [B]: the mean of the K = (19 F + 10) // 20 smallest, NaN sorting last."""
+    F = v.shape[1]
+    if F == 0:
+        return torch.full((v.shape[0],), float("nan"), dtype=torch.float64)
+    K = (19 * F + 10) // 20
+    return torch.sort(v, dim=1).values[:, :K].mean(1)
+
+
+def _llr_wss_seg(s: torch.Tensor, h: torch.Tensor, sample_rate: int):
+    """(llr, wss, seg_snr) [B] float64 of [B, n] float64 rows, n >= win."""
+    hop, win = sdr_geometry(sample_rate)
+    P = composite_order(sample_rate)
+    nfft = 1 << (2 * win - 1).bit_length()
+    t = torch.arange(1, win + 1, dtype=torch.float64)
+    w = 0.5 * (1 - torch.cos(2 * math.pi * t / (win + 1)))
+    fs = s.unfold(1, win, hop) * w
+    fh = h.unfold(1, win, hop) * w
+    fd = (h - s).unfold(1, win, hop) * w
+    seg = (10 * torch.log10(fs.square().sum(2) / (fd.square().sum(2) + 1e-10) + 1e-10)).clamp(-10, 35).mean(1)
+    Rs = torch.stack([(fs[..., :win - k] * fs[..., k:]).sum(-1) for k in range(P + 1)], -1)
+    Rh = torch.stack([(fh[..., :win - k] * fh[..., k:]).sum(-1) for k in range(P + 1)], -1)
+    As, Ah = _lpc(Rs, P), _lpc(Rh, P)
+    lag = (torch.arange(P + 1)[:, None] - torch.arange(P + 1)[None, :]).abs()
+    Tm = Rs[..., lag]  # [B, F, P + 1, P + 1]
+    quad = lambda A: torch.einsum("bfi,bfij,bfj->bf", A, Tm, A)  # noqa: E731
+    llr = torch.log(quad(Ah) / quad(As))
+    G = _wss_filters(int(sample_rate), nfft)
+    H = nfft // 2
+    es = 10 * torch.log10((torch.fft.rfft(fs, nfft).abs().square()[..., :H] @ G.T).clamp_min(1e-10))
+    eh = 10 * torch.log10((torch.fft.rfft(fh, nfft).abs().square()[..., :H] @ G.T).clamp_min(1e-10))
+
+    def weights(e):
+        return 20 / (20 + e.max(-1, keepdim=True).values - e[..., :-1]) / (1 + _nearest_peaks(e) - e[..., :-1])
+
+    W = (weights(es) + weights(eh)) / 2
+    dsl = (es[..., 1:] - es[..., :-1]) - (eh[..., 1:] - eh[..., :-1])
+    wss = (W * dsl.square()).sum(-1) / W.sum(-1)
+    return _trimmed_mean(llr), _trimmed_mean(wss), seg
+
+
+def composite(clean: torch.Tensor, noisy: torch.Tensor, sample_rate: int = 16000, short_ok: bool = False):
+    """[B, n] rows at ``sample_rate`` (8000 or 16000) -> (csig, cbak, covl, pesq, llr, wss, seg_snr),
+    [B] float64 each.  Rows too short for PESQ: RuntimeError as ``pesq``, or NaN in pesq and the
+    composites with ``short_ok``."""
+    B, n = clean.shape
+    nan = torch.full((B,), float("nan"), dtype=torch.float64)
+    if n == 0:
+        return tuple(nan.clone() for _ in range(7))
+    c16, n16 = clean.to(torch.float32), noisy.to(torch.float32)
+    if int(sample_rate) != 16000:
+        from .resample import Resample
+        rs = Resample(int(sample_rate), 16000)
+        c16, n16 = rs(c16), rs(n16)
+    if pesq_frames(c16.shape[1]) < 20 and short_ok:
+        mos = nan.clone()
+    else:
+        mos = pesq(c16, n16)
+    s = clean.to(torch.float64)
+    h = noisy.to(torch.float64)
+    hop, win = sdr_geometry(sample_rate)
+    if n >= win:
+        parts = [_llr_wss_seg(s[i:i + _COMPOSITE_ROWS], h[i:i + _COMPOSITE_ROWS], sample_rate)
+                 for i in range(0, B, _COMPOSITE_ROWS)]
+        llr, wss, seg = (torch.cat([p[k] for p in parts]) for k in range(3))
+    else:
+        llr, wss, seg = nan.clone(), nan.clone(), nan.clone()
+    csig = (3.093 - 1.029 * llr + 0.603 * mos - 0.009 * wss).clamp(1, 5)
+    cbak = (1.634 + 0.478 * mos - 0.007 * wss + 0.063 * seg).clamp(1, 5)
+    covl = (1.594 + 0.805 * mos - 0.512 * llr - 0.007 * wss).clamp(1, 5)
+    bad = ~(torch.isfinite(s).all(1) & torch.isfinite(h).all(1))
+    return tuple(torch.where(bad, nan, v) for v in (csig, cbak, covl, mos, llr, wss, seg))

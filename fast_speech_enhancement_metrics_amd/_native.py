@@ -24,8 +24,11 @@ FSEM_ELAUNCH = -3
 FSEM_ESHORT = -4
 FSEM_ERATE = -5
 
+COMPOSITE_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_composite.so")
+
 _lock = threading.Lock()
 _lib = None
+_composite_lib = None
 
 _c_i64 = ctypes.c_int64
 _c_i32 = ctypes.c_int32
@@ -79,6 +82,13 @@ SIGNATURES = {
     "fsem_sdr_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32]),
     "fsem_sdr_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
                                      _c_sz, _vp]),
+}
+# every symbol include/fsem_composite.h declares (libfsem_composite.so)
+COMPOSITE_SIGNATURES = {
+    "fsem_composite_chunk": (_c_i64, [_c_i32]),
+    "fsem_composite_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32]),
+    "fsem_composite_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _c_sz, _vp]),
 }
 ALIGN_MAX_SEGMENTS = 32  # include/fsem.h FSEM_ALIGN_MAX_SEGMENTS
 PESQ_MAX_BAD = 16  # include/fsem.h FSEM_PESQ_MAX_BAD
@@ -334,6 +344,34 @@ def load() -> ctypes.CDLL:
                 fn.argtypes = args
             _lib = lib
     return _lib
+
+
+def load_composite() -> ctypes.CDLL:
+    """Load (once) and return libfsem_composite.so (include/fsem_composite.h), after libfsem.so,
+    which it links against; raises if it is missing or not the build of this tree's sources."""
+    global _composite_lib
+    if _composite_lib is not None:
+        return _composite_lib
+    load()
+    with _lock:
+        if _composite_lib is None:
+            if not os.path.exists(COMPOSITE_LIB_PATH):
+                raise ImportError(
+                    f"fsem Composite engine not built: {COMPOSITE_LIB_PATH} is missing "
+                    "(run `python -m fast_speech_enhancement_metrics_amd._build`)")
+            from . import _build
+            if all(os.path.exists(d) for d in _build.deps()):
+                have, want = _build.library_build_id(COMPOSITE_LIB_PATH), _build.source_hash()
+                if have != want:
+                    raise ImportError(f"fsem Composite engine {COMPOSITE_LIB_PATH} is stale (build id {have}, sources "
+                                      f"{want}): rebuild it with `python -m fast_speech_enhancement_metrics_amd._build`")
+            lib = ctypes.CDLL(COMPOSITE_LIB_PATH, mode=ctypes.RTLD_LOCAL)
+            for name, (res, args) in COMPOSITE_SIGNATURES.items():
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
+            _composite_lib = lib
+    return _composite_lib
 
 
 def check(rc: int, what: str) -> None:

@@ -1,0 +1,192 @@
+"""Composite metric (CSIG, CBAK, COVL with PESQ, LLR, WSS, SegSNR) on the HIP engine
+(csrc/composite.hip) against the float64 statement of the definitions (tests/composite_cases.py):
+parity at both rates, frame and chunk edges, long rows through the radix select, silent clean
+frames, row layouts, streams, non-finite rows, devices= and the CPU mode."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from fast_speech_enhancement_metrics_amd import PESQ, Composite, _native
+
+from . import composite_cases as cc
+from . import sdr_cases as sc
+
+pytestmark = pytest.mark.gpu
+
+
+def _bits(ts):
+    return [t.cpu().numpy().view(np.uint32) for t in ts]
+
+
+def assert_bitwise(got, want, what=""):
+    for name, g, w in zip(Composite.KEYS, _bits(got), _bits(want)):
+        np.testing.assert_array_equal(g, w, err_msg=f"{what} {name}")
+
+
+def assert_pesq_is_the_class(got, c, n, sr, lengths=None, what=""):
+    """The PESQ key is what PESQ(sr, use_gpu=True).scores gives for the same rows and lengths."""
+    want = PESQ(sr, use_gpu=True).scores(c, n, lengths, sample_rate=sr)
+    np.testing.assert_array_equal(got[3].cpu().numpy(), want.cpu().numpy(), err_msg=f"{what} PESQ key")  # (NaN == NaN)
+
+
+@pytest.fixture(scope="module", params=[8000, 16000])
+def rows(request):
+    """The parity rows of one rate (host), their float64 LLR / WSS and a metric."""
+    sr = request.param
+    c, n = cc.parity_rows(sr)
+    return sr, c, n, cc.expected_llr_wss(c, n, sr), Composite(sr, use_gpu=True)
+
+
+def test_parity_and_int16_scale(rows):
+    sr, c, n, want, m = rows
+    cg, ng = c.cuda(), n.cuda()
+    got = m.scores(cg, ng)
+    assert len(got) == 7 and all(g.is_cuda and g.dtype == torch.float32 and g.shape == (4,) for g in got)
+    cc.assert_scores(got, c, n, sr, what=f"gpu {sr}", want=want)
+    assert np.isfinite(cc.to_np(got)).all()
+    assert_pesq_is_the_class(got, cg, ng, sr, what=f"gpu {sr}")
+    cs, ns = c * 32768, n * 32768  # (exact: powers of two)
+    got = m.scores(cs.cuda(), ns.cuda())
+    cc.assert_scores(got, cs, ns, sr, what=f"gpu {sr} x32768")
+    assert_pesq_is_the_class(got, cs.cuda(), ns.cuda(), sr, what=f"gpu {sr} x32768")
+
+
+def test_frame_and_chunk_edges(rows):
+    sr, m = rows[0], rows[4]
+    lib = _native.load_composite()
+    hop, win = sc.hop_win(sr)
+    C = lib.fsem_composite_chunk(sr)
+    assert C == 16 * hop
+    c, n, lens = cc.edge_rows(sr, C)
+    cg, ng = c.cuda(), n.cuda()
+    got = m.scores(cg, ng, lengths=lens)
+    cc.assert_scores(got, c, n, sr, lengths=lens, what=f"gpu edges {sr}", atol_llr=cc.ATOL_LLR_EDGE,
+                     atol_wss=cc.ATOL_WSS_EDGE)
+    assert_pesq_is_the_class(got, cg, ng, sr, lengths=lens, what=f"gpu edges {sr}")
+    for b, k in enumerate(lens):
+        if k == 0:
+            continue  # (a batch needs a sample; the row's NaNs are checked above)
+        kc = max(k, 5376 * sr // 16000)  # (a capacity PESQ's whole-batch form takes as well)
+        alone = m.scores(cg[b:b + 1, :kc], ng[b:b + 1, :kc], lengths=[k])
+        assert_bitwise([g[b:b + 1] for g in got], alone, f"row {b} (n = {k}) alone")
+
+
+def test_long_row_through_the_select(rows):
+    """A row of about 8000 frames (the row means' radix select has no length limit): 40 hops of
+    speech repeated, so the frame values repeat with period 40 and the float64 side stays small;
+    the repeats are exact ties at the K-th value."""
+    sr, m = rows[0], rows[4]
+    hop, win = sc.hop_win(sr)
+    period, reps = 40, 200
+    c, n = sc.speech_rows(1, period * hop, sr, seed=29, snr_high=20)
+    cl, nl = c.repeat(1, reps), n.repeat(1, reps)
+    F = (cl.shape[1] - win) // hop + 1
+    assert F == period * reps - 3
+    llr, wss = cc.frame_values(cl[0, :period * hop + win - hop].numpy(), nl[0, :period * hop + win - hop].numpy(), sr)
+    assert len(llr) == period
+    idx = np.arange(F) % period
+    want = np.array([[cc.trimmed_mean(llr[idx])], [cc.trimmed_mean(wss[idx])]])
+    got = m.scores(cl.cuda(), nl.cuda())
+    g = cc.to_np(got)
+    for name, k, atol in (("LLR", 4, cc.ATOL_LLR), ("WSS", 5, cc.ATOL_WSS)):
+        err = abs(g[k, 0] - want[k - 4, 0])
+        print(f"gpu long row {sr} {name}: |got - float64 definition| = {err:.3e} over {F} frames")
+        assert err <= atol, (name, g[k, 0], want[k - 4, 0])
+    cc.assert_composites(g, f"gpu long row {sr}")
+    assert np.isfinite(g).all()
+
+
+@pytest.mark.parametrize("zeroed_ms", [75, 187.5])
+def test_silent_clean_head(rows, zeroed_ms):
+    """Digitally silent clean frames: NaN LLR frames (NaN row LLR once more than F - K of them), and
+    clean band energies that sit exactly on the 1e-10 floor (WSS within its bar)."""
+    sr, m = rows[0], rows[4]
+    c, n = cc.silent_head_rows(sr, int(zeroed_ms * sr / 1000))
+    want = cc.expected_llr_wss(c, n, sr)
+    assert np.isnan(want[0, 0]) == (zeroed_ms > 100) and np.isfinite(want[1, 0])
+    got = m.scores(c.cuda(), n.cuda())
+    cc.assert_scores(got, c, n, sr, what=f"gpu silent head {sr} {zeroed_ms} ms", want=want)
+
+
+def test_layouts(rows):
+    sr, c, n, _, m = rows
+    L = c.shape[1] - 3  # L % 4 != 0
+    assert L % 4
+    cg, ng = c.cuda(), n.cuda()
+    base = m.scores(cg[:, :L].contiguous(), ng[:, :L].contiguous())
+    want = cc.assert_scores(base, c[:, :L], n[:, :L], sr, what=f"gpu {sr} L % 4 != 0")
+    cc.assert_scores(m.scores(cg[:, :L], ng[:, :L]), c[:, :L], n[:, :L], sr, what="gpu strided view, L % 4 != 0",
+                     want=want)
+    L4 = c.shape[1] - 400
+    v = m.scores(cg[:, :L4], ng[:, :L4])  # ld > L, no copy
+    cc.assert_scores(v, c[:, :L4], n[:, :L4], sr, what="gpu strided view")
+    # rows that do not start on 16-byte boundaries
+    wide_c = torch.zeros(4, c.shape[1] + 3, device="cuda")
+    wide_n = torch.zeros(4, c.shape[1] + 3, device="cuda")
+    wide_c[:, 1:L4 + 1], wide_n[:, 1:L4 + 1] = cg[:, :L4], ng[:, :L4]
+    assert_bitwise(m.scores(wide_c[:, 1:L4 + 1], wide_n[:, 1:L4 + 1]), v, "unaligned rows")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        s = m.scores(cg[:, :L], ng[:, :L])
+    side.synchronize()
+    assert_bitwise(s, base, "side stream")
+
+
+def test_nonfinite_rows(rows):
+    sr, c, n, _, m = rows
+    c2, n2 = c.clone(), n.clone()
+    n2[1, 5000] = float("nan")
+    c2[2, c.shape[1] - 1] = float("inf")
+    base, got = m.scores(c.cuda(), n.cuda()), m.scores(c2.cuda(), n2.cuda())
+    for g in got:
+        assert torch.isnan(g[[1, 2]]).all()
+    assert_bitwise([g[[0, 3]] for g in got], [b[[0, 3]] for b in base], "finite rows beside non-finite ones")
+
+
+def test_devices_fan_out_and_drop_in(rows):
+    sr, c, n, _, m = rows
+    m2 = Composite(sr, use_gpu=True, devices=[0, 0])
+    cg, ng = c.cuda(), n.cuda()
+    assert_bitwise(m2.scores(cg, ng), m.scores(cg, ng), "devices=[0, 0]")
+    lens = [c.shape[1], 3000, c.shape[1] - 1, 479]
+    one = m.scores(cg, ng, lengths=lens)
+    assert_bitwise(m2.scores(cg, ng, lengths=lens), one, "devices=[0, 0] with lengths")
+    host = [v.cpu().numpy() for v in one]
+    for metric in (m, m2):
+        res = metric(cg, ng, lengths=lens)
+        assert [tuple(r) for r in res] == [Composite.KEYS] * 4
+        for b, r in enumerate(res):
+            for k, key in enumerate(Composite.KEYS):
+                np.testing.assert_array_equal(np.float32(r[key]), host[k][b])
+    # lists of utterances
+    res = m([c[b, :k].cuda() for b, k in enumerate(lens)], [n[b, :k].cuda() for b, k in enumerate(lens)])
+    for b, r in enumerate(res):
+        for k, key in enumerate(Composite.KEYS):
+            np.testing.assert_array_equal(np.float32(r[key]), host[k][b])
+
+
+def test_cpu_mode_agrees(rows):
+    sr, c, n, want, m = rows
+    cpu = cc.to_np(Composite(sr, use_gpu=False).scores(c, n))
+    gpu = cc.to_np(m.scores(c.cuda(), n.cuda()))
+    for name, k, atol in (("LLR", 4, cc.ATOL_LLR), ("WSS", 5, cc.ATOL_WSS), ("SegSNR", 6, sc.ATOL_SEG)):
+        err = float(np.abs(cpu[k] - gpu[k]).max())
+        print(f"gpu vs cpu mode {sr} {name}: worst difference {err:.3e}")
+        assert err <= atol, (name, cpu[k], gpu[k])
+
+
+def test_abi_refuses_before_launch():
+    lib = _native.load_composite()
+    x = torch.zeros(4, 8000, device="cuda")
+    o = torch.zeros(7, 4, device="cuda")
+    p = ctypes.c_void_p
+    args = (p(x.data_ptr()), p(x.data_ptr()), 4, 8000, 8000, None)
+    outs = tuple(p(o[k].data_ptr()) for k in range(7))
+    for sr in (3999, 22050, 200000):
+        assert lib.fsem_composite_f32(*args, sr, *outs, p(x.data_ptr()), 1 << 20, None) == _native.FSEM_ERATE
+    assert lib.fsem_composite_f32(*args, 16000, *outs, p(x.data_ptr()), 16, None) == _native.FSEM_EWORKSPACE
+    torch.cuda.synchronize()
+    assert (o == 0).all()
