@@ -1,10 +1,11 @@
-"""MI355X-native batched PESQ-wb and STOI/ESTOI (drop-in for kcoost/fast_speech_enhancement_metrics).
+"""MI355X-native batched PESQ-wb, STOI/ESTOI and LSD (drop-in for kcoost/fast_speech_enhancement_metrics).
 
     from fast_speech_enhancement_metrics_amd import PESQ, STOI
     PESQ(sample_rate=16000, use_gpu=True)(clean, denoised)  -> [{"PESQ": ...}, ...]
     STOI(sample_rate=16000, use_gpu=True)(clean, denoised)  -> [{"STOI": ..., "ESTOI": ...}, ...]
     PESQ_STOI(16000, use_gpu=True)(clean, denoised)        -> [{"PESQ", "STOI", "ESTOI"}, ...]  (one pass)
     SDR(sample_rate=16000, use_gpu=True)(clean, denoised)   -> [{"SI-SDR", "SNR", "SegSNR"}, ...]  (extension)
+    LSD(sample_rate=16000, use_gpu=True)(clean, denoised)   -> [{"LSD": ...}, ...]  (the reference's LSD)
     Composite(16000, use_gpu=True)(clean, denoised)         -> [{"CSIG", "CBAK", "COVL", "PESQ", "LLR", "WSS", "SegSNR"}, ...]  (extension)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
@@ -15,6 +16,7 @@ from .STOI import STOI
 from .joint import PESQ_STOI
 from .SDR import SDR
 from .Composite import Composite
+from .LSD import LSD
 from .alignment import time_align
 
-__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "time_align"]
+__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "LSD", "time_align"]

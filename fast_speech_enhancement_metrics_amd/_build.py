@@ -2,8 +2,8 @@
 
     python -m fast_speech_enhancement_metrics_amd._build
 
-Output: fast_speech_enhancement_metrics_amd/lib/libfsem.so and libfsem_composite.so (git-ignored, travels with the
-repo snapshot to the GPU box).  Cross-compiles without a GPU.
+Output: fast_speech_enhancement_metrics_amd/lib/libfsem.so, libfsem_composite.so and libfsem_lsd.so (git-ignored,
+travels with the repo snapshot to the GPU box).  Cross-compiles without a GPU.
 """
 from __future__ import annotations
 
@@ -43,6 +43,11 @@ HEADER_ABI = os.path.join(PKG, "..", "include", "fsem.h")
 COMPOSITE_LIB = os.path.join(LIBDIR, "libfsem_composite.so")
 COMPOSITE_SOURCES = ["composite.hip"]
 COMPOSITE_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_composite.h")
+# the LSD metric's engine: a third library, for the same reason; it uses fsem_common.h (the Arena,
+# the launch helpers) and none of libfsem.so's symbols, so it links alone
+LSD_LIB = os.path.join(LIBDIR, "libfsem_lsd.so")
+LSD_SOURCES = ["lsd.hip"]
+LSD_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_lsd.h")
 ARCH = os.environ.get("FSEM_OFFLOAD_ARCH", "gfx950")
 # code-generation flags; the target (--offload-arch=ARCH) is added at build time and recorded in
 # the library on its own (FSEM_BUILD_ARCH): a library built for another target is refused at
@@ -65,7 +70,8 @@ def _hipcc() -> str:
 
 def deps() -> list:
     """Every file whose content the library depends on."""
-    return [os.path.join(CSRC, f) for f in SOURCES + HEADERS + COMPOSITE_SOURCES] + [HEADER_ABI, COMPOSITE_HEADER_ABI]
+    return [os.path.join(CSRC, f) for f in SOURCES + HEADERS + COMPOSITE_SOURCES + LSD_SOURCES] + \
+           [HEADER_ABI, COMPOSITE_HEADER_ABI, LSD_HEADER_ABI]
 
 
 def source_hash() -> str:
@@ -109,7 +115,9 @@ def _stale() -> bool:
     (content hash: an edited header or a changed SOURCE_FLAGS entry rebuilds; a touched file
     whose content is unchanged does not), or for another target than ARCH."""
     want = source_hash()
-    return library_build_id(LIB) != want or library_build_arch(LIB) != ARCH or library_build_id(COMPOSITE_LIB) != want
+    return library_build_id(LIB) != want or library_build_arch(LIB) != ARCH or \
+        library_build_id(COMPOSITE_LIB) != want or library_build_id(LSD_LIB) != want or \
+        library_build_arch(LSD_LIB) != ARCH
 
 
 def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> str:
@@ -127,7 +135,7 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
     objs = []
     try:
         procs = []
-        for src in SOURCES + ([] if stamps else COMPOSITE_SOURCES):  # one object per source (per-source flags, compiled in parallel), one library
+        for src in SOURCES + ([] if stamps else COMPOSITE_SOURCES + LSD_SOURCES):  # one object per source (per-source flags, compiled in parallel), one library
             obj = os.path.join(objdir, src.replace(".hip", ".o"))
             cmd = base + SOURCE_FLAGS.get(src, []) + ["-c", "-o", obj, os.path.join(CSRC, src)]
             if verbose:
@@ -137,7 +145,8 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
         for p, cmd in procs:
             if p.wait() != 0:
                 raise subprocess.CalledProcessError(p.returncode, cmd)
-        cobjs = [] if stamps else objs[len(SOURCES):]
+        cobjs = [] if stamps else objs[len(SOURCES):len(SOURCES) + len(COMPOSITE_SOURCES)]
+        lobjs = [] if stamps else objs[len(SOURCES) + len(COMPOSITE_SOURCES):]
         tmp = f"{lib}.{os.getpid()}.tmp"
         cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + objs[:len(SOURCES)]
         if verbose:
@@ -152,6 +161,13 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
                 print(" ".join(cmd))
             subprocess.check_call(cmd, cwd=CSRC)
             os.replace(tmp, COMPOSITE_LIB)
+        if lobjs:  # libfsem_lsd.so stands alone (no symbol of libfsem.so)
+            tmp = f"{LSD_LIB}.{os.getpid()}.tmp"
+            cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + lobjs
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd, cwd=CSRC)
+            os.replace(tmp, LSD_LIB)
     finally:
         shutil.rmtree(objdir, ignore_errors=True)
     return lib

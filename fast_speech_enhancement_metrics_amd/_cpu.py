@@ -705,6 +705,24 @@ def sdr(clean: torch.Tensor, noisy: torch.Tensor, sample_rate: int = 16000, zero
     return tuple(torch.where(bad, nan, v) for v in (si, snr, seg))
 
 
+# ----------------------------------------------------------------------------- LSD
+# Log-spectral distance (the reference's LSD.py:32-52; engine: csrc/lsd.hip, definition:
+# include/fsem_lsd.h), float64 inside.
+def lsd(clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
+    """[B, n] 16 kHz rows -> lsd [B] float32.  The reference's operations (scale, centred 512-point
+    STFT with hop 256 and a periodic Hann window, log ratio, root mean square over bins, mean over
+    frames) on float64 copies of the rows, on the rows' device; n = 0 is one all-zero frame."""
+    s = clean.to(torch.float64)
+    h = noisy.to(torch.float64)
+    a = (s * h).sum(1, keepdim=True) / (h.square().sum(1, keepdim=True) + 1e-8)
+    x = torch.nn.functional.pad(torch.cat([s, h * a]), (256, 256))  # center=True, pad_mode="constant"
+    w = torch.hann_window(512, dtype=torch.float64, device=x.device)
+    mag = torch.stft(x, n_fft=512, hop_length=256, window=w, center=False, return_complex=True).abs()
+    S, H = mag[:s.shape[0]], mag[s.shape[0]:]
+    v = torch.log(S.square() / (H + 1e-8).square() + 1e-8).square().mean(1).sqrt().mean(1)
+    return v.to(torch.float32)
+
+
 # ----------------------------------------------------------------------------- Composite family
 # CSIG, CBAK, COVL with LLR and WSS (Hu & Loizou 2008; not in the reference; engine:
 # csrc/composite.hip, definitions: include/fsem_composite.h), float64, all frames of a chunk of

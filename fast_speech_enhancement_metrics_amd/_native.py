@@ -25,10 +25,12 @@ FSEM_ESHORT = -4
 FSEM_ERATE = -5
 
 COMPOSITE_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_composite.so")
+LSD_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_lsd.so")
 
 _lock = threading.Lock()
 _lib = None
 _composite_lib = None
+_lsd_lib = None
 
 _c_i64 = ctypes.c_int64
 _c_i32 = ctypes.c_int32
@@ -89,6 +91,13 @@ COMPOSITE_SIGNATURES = {
     "fsem_composite_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32]),
     "fsem_composite_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp, _c_sz, _vp]),
+}
+# every symbol include/fsem_lsd.h declares (libfsem_lsd.so)
+LSD_SIGNATURES = {
+    "fsem_lsd_frames": (_c_i64, [_c_i64]),
+    "fsem_lsd_chunk": (_c_i64, []),
+    "fsem_lsd_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "fsem_lsd_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
 }
 ALIGN_MAX_SEGMENTS = 32  # include/fsem.h FSEM_ALIGN_MAX_SEGMENTS
 PESQ_MAX_BAD = 16  # include/fsem.h FSEM_PESQ_MAX_BAD
@@ -372,6 +381,34 @@ def load_composite() -> ctypes.CDLL:
                 fn.argtypes = args
             _composite_lib = lib
     return _composite_lib
+
+
+def load_lsd() -> ctypes.CDLL:
+    """Load (once) and return libfsem_lsd.so (include/fsem_lsd.h), after libfsem.so (one HIP runtime,
+    one staleness check); raises if it is missing or not the build of this tree's sources."""
+    global _lsd_lib
+    if _lsd_lib is not None:
+        return _lsd_lib
+    load()
+    with _lock:
+        if _lsd_lib is None:
+            if not os.path.exists(LSD_LIB_PATH):
+                raise ImportError(
+                    f"fsem LSD engine not built: {LSD_LIB_PATH} is missing "
+                    "(run `python -m fast_speech_enhancement_metrics_amd._build`)")
+            from . import _build
+            if all(os.path.exists(d) for d in _build.deps()):
+                have, want = _build.library_build_id(LSD_LIB_PATH), _build.source_hash()
+                if have != want:
+                    raise ImportError(f"fsem LSD engine {LSD_LIB_PATH} is stale (build id {have}, sources "
+                                      f"{want}): rebuild it with `python -m fast_speech_enhancement_metrics_amd._build`")
+            lib = ctypes.CDLL(LSD_LIB_PATH, mode=ctypes.RTLD_LOCAL)
+            for name, (res, args) in LSD_SIGNATURES.items():
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
+            _lsd_lib = lib
+    return _lsd_lib
 
 
 def check(rc: int, what: str) -> None:
