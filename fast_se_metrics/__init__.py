@@ -1,8 +1,9 @@
 """Drop-in import path of the reference package: ``from fast_se_metrics import PESQ, STOI``.
 
 The package exports the hot-path metrics (PESQ-wb, STOI/ESTOI); LSD is provided under its module
-path (``from fast_se_metrics.LSD import LSD``).  SDR, DNSMOS and SpeechBERTScore of the reference
-are out of scope.
+path (``from fast_se_metrics.LSD import LSD``).  SDR, the 512-tap BSS-eval SDR, is provided under
+its module path too (``from fast_se_metrics.SDR import SDR``); DNSMOS and SpeechBERTScore of the
+reference are out of scope.
 """
 from fast_se_metrics.PESQ import PESQ  # noqa: F401  (module path first, then the class, as the reference)
 from fast_se_metrics.STOI import STOI  # noqa: F401

@@ -1,4 +1,4 @@
-"""MI355X-native batched PESQ-wb, STOI/ESTOI and LSD (drop-in for kcoost/fast_speech_enhancement_metrics).
+"""MI355X-native batched PESQ-wb, STOI/ESTOI, LSD and BSS-eval SDR (drop-in for kcoost/fast_speech_enhancement_metrics).
 
     from fast_speech_enhancement_metrics_amd import PESQ, STOI
     PESQ(sample_rate=16000, use_gpu=True)(clean, denoised)  -> [{"PESQ": ...}, ...]
@@ -6,6 +6,7 @@
     PESQ_STOI(16000, use_gpu=True)(clean, denoised)        -> [{"PESQ", "STOI", "ESTOI"}, ...]  (one pass)
     SDR(sample_rate=16000, use_gpu=True)(clean, denoised)   -> [{"SI-SDR", "SNR", "SegSNR"}, ...]  (extension)
     LSD(sample_rate=16000, use_gpu=True)(clean, denoised)   -> [{"LSD": ...}, ...]  (the reference's LSD)
+    BSSSDR(sample_rate=16000, use_gpu=True)(clean, denoised) -> [{"SDR": ...}, ...]  (the reference's SDR)
     Composite(16000, use_gpu=True)(clean, denoised)         -> [{"CSIG", "CBAK", "COVL", "PESQ", "LLR", "WSS", "SegSNR"}, ...]  (extension)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
@@ -17,6 +18,7 @@ from .joint import PESQ_STOI
 from .SDR import SDR
 from .Composite import Composite
 from .LSD import LSD
+from .BSSSDR import BSSSDR
 from .alignment import time_align
 
-__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "LSD", "time_align"]
+__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "LSD", "BSSSDR", "time_align"]

@@ -2,8 +2,8 @@
 
     python -m fast_speech_enhancement_metrics_amd._build
 
-Output: fast_speech_enhancement_metrics_amd/lib/libfsem.so, libfsem_composite.so and libfsem_lsd.so (git-ignored,
-travels with the repo snapshot to the GPU box).  Cross-compiles without a GPU.
+Output: fast_speech_enhancement_metrics_amd/lib/libfsem.so, libfsem_composite.so, libfsem_lsd.so and
+libfsem_bsssdr.so (git-ignored, travels with the repo snapshot to the GPU box).  Cross-compiles without a GPU.
 """
 from __future__ import annotations
 
@@ -48,6 +48,10 @@ COMPOSITE_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_composite.h")
 LSD_LIB = os.path.join(LIBDIR, "libfsem_lsd.so")
 LSD_SOURCES = ["lsd.hip"]
 LSD_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_lsd.h")
+# the BSSSDR metric's engine (the reference's SDR): a fourth library, as libfsem_lsd.so
+BSSSDR_LIB = os.path.join(LIBDIR, "libfsem_bsssdr.so")
+BSSSDR_SOURCES = ["bsssdr.hip"]
+BSSSDR_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_bsssdr.h")
 ARCH = os.environ.get("FSEM_OFFLOAD_ARCH", "gfx950")
 # code-generation flags; the target (--offload-arch=ARCH) is added at build time and recorded in
 # the library on its own (FSEM_BUILD_ARCH): a library built for another target is refused at
@@ -70,8 +74,9 @@ def _hipcc() -> str:
 
 def deps() -> list:
     """Every file whose content the library depends on."""
-    return [os.path.join(CSRC, f) for f in SOURCES + HEADERS + COMPOSITE_SOURCES + LSD_SOURCES] + \
-           [HEADER_ABI, COMPOSITE_HEADER_ABI, LSD_HEADER_ABI]
+    return [os.path.join(CSRC, f) for f in SOURCES + HEADERS + COMPOSITE_SOURCES + LSD_SOURCES +
+                                         BSSSDR_SOURCES] + \
+           [HEADER_ABI, COMPOSITE_HEADER_ABI, LSD_HEADER_ABI, BSSSDR_HEADER_ABI]
 
 
 def source_hash() -> str:
@@ -117,7 +122,8 @@ def _stale() -> bool:
     want = source_hash()
     return library_build_id(LIB) != want or library_build_arch(LIB) != ARCH or \
         library_build_id(COMPOSITE_LIB) != want or library_build_id(LSD_LIB) != want or \
-        library_build_arch(LSD_LIB) != ARCH
+        library_build_arch(LSD_LIB) != ARCH or library_build_id(BSSSDR_LIB) != want or \
+        library_build_arch(BSSSDR_LIB) != ARCH
 
 
 def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> str:
@@ -135,7 +141,7 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
     objs = []
     try:
         procs = []
-        for src in SOURCES + ([] if stamps else COMPOSITE_SOURCES + LSD_SOURCES):  # one object per source (per-source flags, compiled in parallel), one library
+        for src in SOURCES + ([] if stamps else COMPOSITE_SOURCES + LSD_SOURCES + BSSSDR_SOURCES):  # one object per source (per-source flags, compiled in parallel), one library
             obj = os.path.join(objdir, src.replace(".hip", ".o"))
             cmd = base + SOURCE_FLAGS.get(src, []) + ["-c", "-o", obj, os.path.join(CSRC, src)]
             if verbose:
@@ -146,7 +152,9 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
             if p.wait() != 0:
                 raise subprocess.CalledProcessError(p.returncode, cmd)
         cobjs = [] if stamps else objs[len(SOURCES):len(SOURCES) + len(COMPOSITE_SOURCES)]
-        lobjs = [] if stamps else objs[len(SOURCES) + len(COMPOSITE_SOURCES):]
+        nl = len(SOURCES) + len(COMPOSITE_SOURCES)
+        lobjs = [] if stamps else objs[nl:nl + len(LSD_SOURCES)]
+        bobjs = [] if stamps else objs[nl + len(LSD_SOURCES):]
         tmp = f"{lib}.{os.getpid()}.tmp"
         cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + objs[:len(SOURCES)]
         if verbose:
@@ -168,6 +176,13 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
                 print(" ".join(cmd))
             subprocess.check_call(cmd, cwd=CSRC)
             os.replace(tmp, LSD_LIB)
+        if bobjs:  # libfsem_bsssdr.so stands alone too
+            tmp = f"{BSSSDR_LIB}.{os.getpid()}.tmp"
+            cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + bobjs
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd, cwd=CSRC)
+            os.replace(tmp, BSSSDR_LIB)
     finally:
         shutil.rmtree(objdir, ignore_errors=True)
     return lib

@@ -723,6 +723,58 @@ def lsd(clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
     return v.to(torch.float32)
 
 
+# ----------------------------------------------------------------------------- BSS-eval SDR
+# The reference's SDR (SDR.py:7-97; engine: csrc/bsssdr.hip, definition: include/fsem_bsssdr.h):
+# float32 normalisation as the reference's, then float64: linear correlations for 512 lags and a
+# Levinson-Durbin recursion for the Toeplitz system, written out (no linalg.solve, no Cholesky).
+def bsssdr(clean: torch.Tensor, noisy: torch.Tensor, load_diag=None, filter_length: int = 512) -> torch.Tensor:
+    """[B, n] 16 kHz rows -> SDR [B] float32 in dB.  NaN for a row whose system is singular (a silent
+    clean row, n = 0, a prediction error <= 0) or that holds a non-finite sample; all rows of the
+    chunk advance through the recursion together."""
+    K = filter_length
+    B, n = clean.shape
+    nan = torch.full((B,), float("nan"), dtype=torch.float32, device=clean.device)
+    if n == 0 or B == 0:
+        return nan
+    s32, h32 = clean.to(torch.float32), noisy.to(torch.float32)
+    finite = torch.isfinite(s32).all(1) & torch.isfinite(h32).all(1)
+    s32 = torch.where(finite[:, None], s32, torch.zeros_like(s32))
+    h32 = torch.where(finite[:, None], h32, torch.zeros_like(h32))
+    # the norms in double, rounded to float32; the clamp and the quotient in float32
+    ns = s32.double().square().sum(1).sqrt().float().clamp(min=1e-6)
+    nh = h32.double().square().sum(1).sqrt().float().clamp(min=1e-6)
+    s = (s32 / ns[:, None]).double()
+    h = (h32 / nh[:, None]).double()
+    nfft = 1 << (n + K - 1).bit_length()  # >= n + K: no wrap-around within K lags
+    Sf = torch.fft.rfft(s, n=nfft)
+    r = torch.fft.irfft(Sf.abs().square(), n=nfft)[:, :K].contiguous()
+    b = torch.fft.irfft(Sf.conj() * torch.fft.rfft(h, n=nfft), n=nfft)[:, :K].contiguous()
+    if load_diag is not None:
+        r[:, 0] += float(load_diag)
+    bad = ~finite | ~(r[:, 0] > 0)
+    r0 = torch.where(bad, torch.ones_like(r[:, 0]), r[:, 0])
+    E = r0.clone()
+    a = torch.zeros(B, K, dtype=torch.float64, device=r.device)  # the predictor [1, a1, ..., am]
+    a[:, 0] = 1.0
+    x = torch.zeros_like(a)
+    x[:, 0] = b[:, 0] / r0
+    for m in range(1, K):
+        rr = r[:, 1:m + 1].flip(1)  # r[m - i], i = 0 ... m - 1
+        acc = (a[:, :m] * rr).sum(1)
+        q = (x[:, :m] * rr).sum(1)
+        k = -acc / E
+        a[:, :m + 1] = a[:, :m + 1] + k[:, None] * a[:, :m + 1].flip(1)
+        E = E * (1.0 - k * k)
+        bad = bad | ~(E > 0)
+        E = torch.where(bad, torch.ones_like(E), E)  # (a row already NaN: keep the arithmetic finite)
+        lam = (b[:, m] - q) / E
+        x[:, :m + 1] = x[:, :m + 1] + lam[:, None] * a[:, :m + 1].flip(1)
+    coh = (b * x).sum(1)
+    ratio = coh / (1.0 - coh).clamp(min=1e-8)
+    val = (10.0 * torch.log10(ratio.clamp(min=1e-8))).to(torch.float32)
+    return torch.where(bad | ~torch.isfinite(coh), nan, val)
+
+
 # ----------------------------------------------------------------------------- Composite family
 # CSIG, CBAK, COVL with LLR and WSS (Hu & Loizou 2008; not in the reference; engine:
 # csrc/composite.hip, definitions: include/fsem_composite.h), float64, all frames of a chunk of

@@ -26,11 +26,13 @@ FSEM_ERATE = -5
 
 COMPOSITE_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_composite.so")
 LSD_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_lsd.so")
+BSSSDR_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_bsssdr.so")
 
 _lock = threading.Lock()
 _lib = None
 _composite_lib = None
 _lsd_lib = None
+_bsssdr_lib = None
 
 _c_i64 = ctypes.c_int64
 _c_i32 = ctypes.c_int32
@@ -98,6 +100,16 @@ LSD_SIGNATURES = {
     "fsem_lsd_chunk": (_c_i64, []),
     "fsem_lsd_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
     "fsem_lsd_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
+}
+# every symbol include/fsem_bsssdr.h declares (libfsem_bsssdr.so)
+BSSSDR_SIGNATURES = {
+    "fsem_bsssdr_filter_length": (_c_i64, []),
+    "fsem_bsssdr_chunk": (_c_i64, []),
+    "fsem_bsssdr_norm_chunk": (_c_i64, []),
+    "fsem_bsssdr_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "fsem_bsssdr_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
+    "fsem_bsssdr_load_diag_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, ctypes.c_double, _vp, _vp,
+                                                 _c_sz, _vp]),
 }
 ALIGN_MAX_SEGMENTS = 32  # include/fsem.h FSEM_ALIGN_MAX_SEGMENTS
 PESQ_MAX_BAD = 16  # include/fsem.h FSEM_PESQ_MAX_BAD
@@ -409,6 +421,34 @@ def load_lsd() -> ctypes.CDLL:
                 fn.argtypes = args
             _lsd_lib = lib
     return _lsd_lib
+
+
+def load_bsssdr() -> ctypes.CDLL:
+    """Load (once) and return libfsem_bsssdr.so (include/fsem_bsssdr.h), after libfsem.so (one HIP
+    runtime, one staleness check); raises if it is missing or not the build of this tree's sources."""
+    global _bsssdr_lib
+    if _bsssdr_lib is not None:
+        return _bsssdr_lib
+    load()
+    with _lock:
+        if _bsssdr_lib is None:
+            if not os.path.exists(BSSSDR_LIB_PATH):
+                raise ImportError(
+                    f"fsem BSSSDR engine not built: {BSSSDR_LIB_PATH} is missing "
+                    "(run `python -m fast_speech_enhancement_metrics_amd._build`)")
+            from . import _build
+            if all(os.path.exists(d) for d in _build.deps()):
+                have, want = _build.library_build_id(BSSSDR_LIB_PATH), _build.source_hash()
+                if have != want:
+                    raise ImportError(f"fsem BSSSDR engine {BSSSDR_LIB_PATH} is stale (build id {have}, sources "
+                                      f"{want}): rebuild it with `python -m fast_speech_enhancement_metrics_amd._build`")
+            lib = ctypes.CDLL(BSSSDR_LIB_PATH, mode=ctypes.RTLD_LOCAL)
+            for name, (res, args) in BSSSDR_SIGNATURES.items():
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
+            _bsssdr_lib = lib
+    return _bsssdr_lib
 
 
 def check(rc: int, what: str) -> None:

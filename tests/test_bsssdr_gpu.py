@@ -1,0 +1,221 @@
+"""BSSSDR metric (the reference's SDR) on the HIP engine (csrc/bsssdr.hip) against the float64
+statement of the definition (tests/bsssdr_cases.py) and the reference's scores: parity, the int16
+scale, ragged rows on each side of every edge of the kernels, row layouts, the resampler, gains,
+delays inside and outside the filter, edge rows, non-finite rows, devices= and the CPU mode."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from fast_speech_enhancement_metrics_amd import BSSSDR, _native
+
+from . import bsssdr_cases as bc
+
+pytestmark = pytest.mark.gpu
+
+
+def _bits(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def assert_bitwise(got, want, what=""):
+    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
+
+
+@pytest.fixture(scope="module")
+def rows16():
+    """The 16 kHz parity rows (host; 4 speech-like, 4 white), their float64 scores, the keep mask
+    and a metric."""
+    cs, ns = bc.speech_rows(4, 32000)
+    cw, nw = bc.white_rows(4, 32000)
+    c, n = torch.cat([cs, cw]), torch.cat([ns, nw])
+    want, keep = bc.expected(c, n)
+    return c, n, want, keep, BSSSDR(16000, use_gpu=True)
+
+
+def test_parity_16k_and_int16_scale(rows16):
+    c, n, want, keep, m = rows16
+    assert keep.sum() >= 7
+    got = m.scores(c.cuda(), n.cuda())
+    assert got.is_cuda and got.dtype == torch.float32 and got.shape == (8,)
+    bc.assert_close(got, want, keep, "gpu 16000")
+    cs, ns = c * 32768, n * 32768  # (exact: powers of two; the normalisation cancels the scale)
+    ws, ks = bc.expected(cs, ns)
+    bc.assert_close(m.scores(cs.cuda(), ns.cuda()), ws, ks, "gpu 16000 x32768")
+    res = m(c.cuda(), n.cuda())
+    assert [tuple(r) for r in res] == [BSSSDR.KEYS] * 8
+    np.testing.assert_array_equal(np.array([r["SDR"] for r in res], np.float32), got.cpu().numpy())
+
+
+def test_golden_against_the_reference(rows16):
+    names = ("bsssdr_16k", "bsssdr_8k", "bsssdr_white")
+    bar = bc.golden_bar(*names)
+    for name in names:
+        c, n, sr, ref, has_ref, ref_ok = bc.golden(name)
+        m = rows16[4] if sr == 16000 else BSSSDR(sr, use_gpu=True)
+        got = m(c.cuda(), n.cuda())
+        bc.assert_close(got, ref, ref_ok, f"gpu call vs reference {name}", atol=bar)
+
+
+def test_8k_rows_through_the_resampler():
+    c, n = bc.speech_rows(4, 16000, sr=8000)
+    m = BSSSDR(8000, use_gpu=True)
+    cg, ng = c.cuda(), n.cuda()
+    c16, n16 = m.prepare_inputs(cg, ng)
+    assert c16.shape == (4, 32000)
+    want, keep = bc.expected(c16, n16)
+    assert keep.sum() >= 3
+    bc.assert_close(m(cg, ng), want, keep, "gpu call 8k vs definition on the resampled rows")
+    bc.assert_close(m.scores(cg, ng, sample_rate=8000), want, keep, "gpu scores 8k")
+
+
+def test_ragged_rows_at_every_edge(rows16):
+    lib = _native.load_bsssdr()
+    assert lib.fsem_bsssdr_filter_length() == 512
+    C, NC = lib.fsem_bsssdr_chunk(), lib.fsem_bsssdr_norm_chunk()
+    lens = bc.ragged_lengths(C, NC)
+    cap = max(lens)
+    c, n = bc.white_rows(len(lens), cap, seed=17)
+    want, keep = bc.expected(c, n, lens)
+    assert keep.all()
+    # whatever the memory past a row's length holds
+    cp, npad = c.clone(), n.clone()
+    for b, k in enumerate(lens):
+        cp[b, k:] = float("nan")
+        npad[b, k:] = 1e30
+    m = rows16[4]
+    cg, ng = cp.cuda(), npad.cuda()
+    got = m.scores(cg, ng, lengths=lens)
+    bc.assert_close(got, want, keep, "gpu ragged rows")
+    # each row alone, and at another batch position (the batch reversed)
+    rev = m.scores(cg.flip(0), ng.flip(0), lengths=lens[::-1])
+    assert_bitwise(rev.flip(0), got, "the batch reversed")
+    for b, k in enumerate(lens):
+        alone = m.scores(cg[b:b + 1, :k], ng[b:b + 1, :k])
+        assert_bitwise(got[b:b + 1], alone, f"row {b} (n = {k}) alone")
+
+
+def test_rows_shorter_than_the_filter(rows16):
+    """Finite or NaN, and bitwise equal alone and in a batch."""
+    lens = [1, 2, 7, 64, 100, 300, 511]
+    c, n = bc.white_rows(len(lens), 512, seed=19)
+    m = rows16[4]
+    cg, ng = c.cuda(), n.cuda()
+    got = m.scores(cg, ng, lengths=lens)
+    assert not torch.isinf(got).any()
+    for b, k in enumerate(lens):
+        assert_bitwise(got[b:b + 1], m.scores(cg[b:b + 1, :k], ng[b:b + 1, :k]), f"row {b} (n = {k}) alone")
+
+
+def test_layouts(rows16):
+    c, n, _, _, m = rows16
+    L = 30001
+    want, keep = bc.expected(c[:, :L], n[:, :L])
+    cg, ng = c.cuda(), n.cuda()
+    base = m.scores(cg[:, :L].contiguous(), ng[:, :L].contiguous())  # L % 4 != 0
+    bc.assert_close(base, want, keep, "gpu L=30001")
+    assert_bitwise(m.scores(cg[:, :L], ng[:, :L]), base, "strided view, L % 4 != 0")
+    L4 = 30000
+    v = m.scores(cg[:, :L4], ng[:, :L4])  # ld = 32000 > L, no copy
+    bc.assert_close(v, *bc.expected(c[:, :L4], n[:, :L4]), "gpu strided view")
+    assert_bitwise(m.scores(cg[:, :L4].contiguous(), ng[:, :L4].contiguous()), v, "ld > L")
+    # rows that do not start on 16-byte boundaries
+    wide_c, wide_n = torch.zeros(8, 32003, device="cuda"), torch.zeros(8, 32003, device="cuda")
+    wide_c[:, 1:L4 + 1], wide_n[:, 1:L4 + 1] = cg[:, :L4], ng[:, :L4]
+    assert_bitwise(m.scores(wide_c[:, 1:L4 + 1], wide_n[:, 1:L4 + 1]), v, "unaligned rows")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        s = m.scores(cg[:, :L], ng[:, :L])
+    side.synchronize()
+    assert_bitwise(s, base, "side stream")
+
+
+def test_gains_and_delays(rows16):
+    m = rows16[4]
+    c, n = bc.delay_rows()
+    want, keep = bc.expected(c, n)
+    assert keep.all() and want[0] > 15 and want[1] < 0
+    bc.assert_close(m.scores(c.cuda(), n.cuda()), want, keep, "gpu delays")
+    x = rows16[0][4:6]
+    g = m.scores(x.cuda(), (0.3 * x).cuda()).cpu().numpy()
+    assert (g >= 60).all() and (g <= 80.001).all()  # h = 0.3 s: +80 dB up to the float32 normalisation
+
+
+def test_edge_semantics(rows16):
+    m = rows16[4]
+    c, n = bc.edge_rows()
+    want, keep = bc.expected(c, n)
+    got = m.scores(c.cuda(), n.cuda())
+    bc.assert_close(got, want, keep, "gpu edge rows")
+    g = got.double().cpu().numpy()
+    assert 60 <= g[0] <= 80.001 and 60 <= g[3] <= 80.001 and g[1] == -80.0 and np.isnan(g[2])
+    # n = 0 in a ragged list beside scored rows, and a batch of no samples
+    lens = [0, 700, 2000]
+    res = m([c[b, :k].cuda() for b, k in enumerate(lens)], [n[b, :k].cuda() for b, k in enumerate(lens)])
+    assert [tuple(r) for r in res] == [BSSSDR.KEYS] * 3
+    bc.assert_close(res, *bc.expected(c[:3], n[:3], lens), "gpu ragged list with an empty row")
+    assert torch.isnan(m.scores(c[:, :0].cuda(), n[:, :0].cuda())).all()
+    # the neighbours of NaN rows are what they are without them
+    assert_bitwise(got[[0, 1, 3, 4]], m.scores(c[[0, 1, 3, 4]].cuda(), n[[0, 1, 3, 4]].cuda()), "beside a NaN row")
+
+
+def test_nonfinite_rows(rows16):
+    c, n, want, keep, m = rows16
+    c2, n2 = c.clone(), n.clone()
+    n2[1, 12345] = float("nan")
+    c2[2, 31999] = float("inf")
+    n2[5, 0] = float("-inf")
+    base, got = m.scores(c.cuda(), n.cuda()), m.scores(c2.cuda(), n2.cuda())
+    assert torch.isnan(got[[1, 2, 5]]).all()
+    assert_bitwise(got[[0, 3, 4, 6, 7]], base[[0, 3, 4, 6, 7]], "finite rows beside non-finite ones")
+
+
+def test_past_grid_limit(rows16):
+    NB = 65537
+    c, n = bc.white_rows(4, 600, seed=23)
+    cg, ng = c.cuda(), n.cuda()
+    m = rows16[4]
+    small = m.scores(cg, ng)
+    reps = -(-NB // 4)
+    big = m.scores(cg.repeat(reps, 1)[:NB].contiguous(), ng.repeat(reps, 1)[:NB].contiguous())
+    np.testing.assert_array_equal(_bits(big), _bits(small)[np.arange(NB) % 4])
+    bc.assert_close(small, *bc.expected(c, n), "gpu 600-sample rows")
+
+
+def test_load_diag(rows16):
+    c, n = rows16[0][4:6], rows16[1][4:6]
+    m = BSSSDR(16000, use_gpu=True)
+    m.load_diag = 0.5
+    cpu = BSSSDR(16000, use_gpu=False)
+    cpu.load_diag = 0.5
+    bc.assert_close(m.scores(c.cuda(), n.cuda()), cpu.scores(c, n).double().numpy(), None, "gpu load_diag vs cpu mode")
+
+
+def test_devices_fan_out_and_cpu_mode(rows16):
+    c, n, want, keep, m = rows16
+    m2 = BSSSDR(16000, use_gpu=True, devices=[0, 0])
+    cg, ng = c[:4].cuda(), n[:4].cuda()
+    lens = [32000, 1000, 30001, 600]
+    one = m.scores(cg, ng, lengths=lens)
+    assert_bitwise(m2.scores(cg, ng, lengths=lens), one, "devices=[0, 0] with lengths")
+    cpu = BSSSDR(16000, use_gpu=False).scores(c, n)
+    bc.assert_close(cpu, want, keep, "cpu 16000")
+    bc.assert_close(m.scores(c.cuda(), n.cuda()), cpu.double().numpy(), keep, "gpu vs cpu mode")
+
+
+def test_abi_refuses_before_launch():
+    lib = _native.load_bsssdr()
+    x = torch.zeros(4, 1000, device="cuda")
+    o = torch.zeros(4, device="cuda")
+    p = ctypes.c_void_p
+    args = (p(x.data_ptr()), p(x.data_ptr()), 4, 1000, 1000, None, p(o.data_ptr()))
+    size = lib.fsem_bsssdr_workspace_bytes(4, 1000)
+    ws = torch.zeros(size, dtype=torch.uint8, device="cuda")
+    assert lib.fsem_bsssdr_f32(*args, p(ws.data_ptr()), 16, None) == _native.FSEM_EWORKSPACE
+    assert lib.fsem_bsssdr_f32(*args, p(ws.data_ptr()), size - 1, None) == _native.FSEM_EWORKSPACE
+    assert lib.fsem_bsssdr_f32(p(x.data_ptr()), p(x.data_ptr()), 4, 1000, 999, None, p(o.data_ptr()),
+                               p(ws.data_ptr()), size, None) == _native.FSEM_EINVAL
+    torch.cuda.synchronize()
+    assert not o.any()  # (nothing ran)
