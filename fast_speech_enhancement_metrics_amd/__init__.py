@@ -7,7 +7,8 @@
     SDR(sample_rate=16000, use_gpu=True)(clean, denoised)   -> [{"SI-SDR", "SNR", "SegSNR"}, ...]  (extension)
     LSD(sample_rate=16000, use_gpu=True)(clean, denoised)   -> [{"LSD": ...}, ...]  (the reference's LSD)
     BSSSDR(sample_rate=16000, use_gpu=True)(clean, denoised) -> [{"SDR": ...}, ...]  (the reference's SDR)
-    Composite(16000, use_gpu=True)(clean, denoised)         -> [{"CSIG", "CBAK", "COVL", "PESQ", "LLR", "WSS", "SegSNR"}, ...]  (extension)
+    DNSMOS(sample_rate=16000, use_gpu=True)(None, denoised) -> [{"SIG", "BAK", "OVRL"}, ...]  (the reference's DNSMOS)
+    Composite(16000, use_gpu=True)(clean, denoised)        -> [{"CSIG", "CBAK", "COVL", "PESQ", "LLR", "WSS", "SegSNR"}, ...]  (extension)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
 """
@@ -19,6 +20,7 @@ from .SDR import SDR
 from .Composite import Composite
 from .LSD import LSD
 from .BSSSDR import BSSSDR
+from .DNSMOS import DNSMOS
 from .alignment import time_align
 
-__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "LSD", "BSSSDR", "time_align"]
+__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "LSD", "BSSSDR", "DNSMOS", "time_align"]

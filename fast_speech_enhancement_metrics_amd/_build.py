@@ -2,8 +2,8 @@
 
     python -m fast_speech_enhancement_metrics_amd._build
 
-Output: fast_speech_enhancement_metrics_amd/lib/libfsem.so, libfsem_composite.so, libfsem_lsd.so and
-libfsem_bsssdr.so (git-ignored, travels with the repo snapshot to the GPU box).  Cross-compiles without a GPU.
+Output: fast_speech_enhancement_metrics_amd/lib/libfsem.so, libfsem_composite.so, libfsem_lsd.so,
+libfsem_bsssdr.so and libfsem_dnsmos.so (git-ignored, travels with the repo snapshot to the GPU box).  Cross-compiles without a GPU.
 """
 from __future__ import annotations
 
@@ -52,6 +52,10 @@ LSD_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_lsd.h")
 BSSSDR_LIB = os.path.join(LIBDIR, "libfsem_bsssdr.so")
 BSSSDR_SOURCES = ["bsssdr.hip"]
 BSSSDR_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_bsssdr.h")
+# the DNSMOS metric's engine (f16 MFMA convolutions): a fifth library, as libfsem_lsd.so
+DNSMOS_LIB = os.path.join(LIBDIR, "libfsem_dnsmos.so")
+DNSMOS_SOURCES = ["dnsmos.hip"]
+DNSMOS_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_dnsmos.h")
 ARCH = os.environ.get("FSEM_OFFLOAD_ARCH", "gfx950")
 # code-generation flags; the target (--offload-arch=ARCH) is added at build time and recorded in
 # the library on its own (FSEM_BUILD_ARCH): a library built for another target is refused at
@@ -75,8 +79,8 @@ def _hipcc() -> str:
 def deps() -> list:
     """Every file whose content the library depends on."""
     return [os.path.join(CSRC, f) for f in SOURCES + HEADERS + COMPOSITE_SOURCES + LSD_SOURCES +
-                                         BSSSDR_SOURCES] + \
-           [HEADER_ABI, COMPOSITE_HEADER_ABI, LSD_HEADER_ABI, BSSSDR_HEADER_ABI]
+                                         BSSSDR_SOURCES + DNSMOS_SOURCES] + \
+           [HEADER_ABI, COMPOSITE_HEADER_ABI, LSD_HEADER_ABI, BSSSDR_HEADER_ABI, DNSMOS_HEADER_ABI]
 
 
 def source_hash() -> str:
@@ -123,7 +127,8 @@ def _stale() -> bool:
     return library_build_id(LIB) != want or library_build_arch(LIB) != ARCH or \
         library_build_id(COMPOSITE_LIB) != want or library_build_id(LSD_LIB) != want or \
         library_build_arch(LSD_LIB) != ARCH or library_build_id(BSSSDR_LIB) != want or \
-        library_build_arch(BSSSDR_LIB) != ARCH
+        library_build_arch(BSSSDR_LIB) != ARCH or library_build_id(DNSMOS_LIB) != want or \
+        library_build_arch(DNSMOS_LIB) != ARCH
 
 
 def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> str:
@@ -141,7 +146,8 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
     objs = []
     try:
         procs = []
-        for src in SOURCES + ([] if stamps else COMPOSITE_SOURCES + LSD_SOURCES + BSSSDR_SOURCES):  # one object per source (per-source flags, compiled in parallel), one library
+        for src in SOURCES + ([] if stamps else COMPOSITE_SOURCES + LSD_SOURCES + BSSSDR_SOURCES +
+                                   DNSMOS_SOURCES):  # one object per source (per-source flags, compiled in parallel), one library
             obj = os.path.join(objdir, src.replace(".hip", ".o"))
             cmd = base + SOURCE_FLAGS.get(src, []) + ["-c", "-o", obj, os.path.join(CSRC, src)]
             if verbose:
@@ -154,7 +160,9 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
         cobjs = [] if stamps else objs[len(SOURCES):len(SOURCES) + len(COMPOSITE_SOURCES)]
         nl = len(SOURCES) + len(COMPOSITE_SOURCES)
         lobjs = [] if stamps else objs[nl:nl + len(LSD_SOURCES)]
-        bobjs = [] if stamps else objs[nl + len(LSD_SOURCES):]
+        nb = nl + len(LSD_SOURCES)
+        bobjs = [] if stamps else objs[nb:nb + len(BSSSDR_SOURCES)]
+        dobjs = [] if stamps else objs[nb + len(BSSSDR_SOURCES):]
         tmp = f"{lib}.{os.getpid()}.tmp"
         cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + objs[:len(SOURCES)]
         if verbose:
@@ -183,6 +191,13 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
                 print(" ".join(cmd))
             subprocess.check_call(cmd, cwd=CSRC)
             os.replace(tmp, BSSSDR_LIB)
+        if dobjs:  # libfsem_dnsmos.so stands alone too
+            tmp = f"{DNSMOS_LIB}.{os.getpid()}.tmp"
+            cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + dobjs
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd, cwd=CSRC)
+            os.replace(tmp, DNSMOS_LIB)
     finally:
         shutil.rmtree(objdir, ignore_errors=True)
     return lib

@@ -915,3 +915,80 @@ def composite(clean: torch.Tensor, noisy: torch.Tensor, sample_rate: int = 16000
     covl = (1.594 + 0.805 * mos - 0.512 * llr - 0.007 * wss).clamp(1, 5)
     bad = ~(torch.isfinite(s).all(1) & torch.isfinite(h).all(1))
     return tuple(torch.where(bad, nan, v) for v in (csig, cbak, covl, mos, llr, wss, seg))
+
+
+# ----------------------------------------------------------------------------- DNSMOS
+# The reference's DNSMOS network (DNSMOS.py) in float32 torch ops from the checkpoint's tensors
+# (a dict of state-dict names -> float32 CPU tensors); engine: csrc/dnsmos.hip.
+DNSMOS_SEGMENT, DNSMOS_HOP = 144160, 16000
+_DNSMOS_POLY = ((0.0052439, -0.39604546, 0.04602535), (1.22083953, 1.60915514, 1.11546468),
+                (-0.08397278, -0.13166888, -0.06766283))
+_DNSMOS_POOL_AFTER = (6, 9, 12)  # max-pool follows conv_layers.6, .9 and .12
+
+
+def dnsmos_segments(n: int) -> int:
+    """Segments of a row of n samples: the row doubled until it holds 144160 samples, then
+    (n' - 144160) // 16000 + 1; 0 for an empty row."""
+    if n < 1:
+        return 0
+    while n < DNSMOS_SEGMENT:
+        n *= 2
+    return (n - DNSMOS_SEGMENT) // DNSMOS_HOP + 1
+
+
+def dnsmos_row_segments(row: torch.Tensor) -> torch.Tensor:
+    """[S, 144160] float32 segments of one unpadded 1-D row (periodic continuation x[i mod n])."""
+    n = row.numel()
+    m = n
+    while m < DNSMOS_SEGMENT:
+        m *= 2
+    return row.to(torch.float32).repeat(m // n).unfold(0, DNSMOS_SEGMENT, DNSMOS_HOP)
+
+
+def dnsmos_features(w: dict, segs: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """[S, 900, 161] log-power image of [S, 144160] segments: log10(max(re^2 + im^2, 1e-12))."""
+    fr = segs.to(dtype).unfold(1, 320, 160)                                    # [S, 900, 320]
+    re = fr @ w["conv_real_stft.weight"].reshape(161, 320).to(dtype).T
+    im = fr @ w["conv_imag_stft.weight"].reshape(161, 320).to(dtype).T
+    return torch.log10(torch.clamp_min(re.square() + im.square(), 1e-12))
+
+
+def dnsmos_network(w: dict, image: torch.Tensor) -> torch.Tensor:
+    """[S, 3] raw outputs of the convolution stack and the dense layers on [S, 900, 161] images."""
+    F = torch.nn.functional
+    h = image.unsqueeze(1)
+    for i in (0, 2, 4, 6, 9, 12, 15):
+        h = F.relu(F.conv2d(h, w[f"conv_layers.{i}.weight"], w[f"conv_layers.{i}.bias"], padding=1))
+        if i in _DNSMOS_POOL_AFTER:
+            h = F.max_pool2d(h, 2)
+    h = h.amax(dim=(2, 3))
+    h = F.relu(F.linear(h, w["output_layers.0.weight"], w["output_layers.0.bias"]))
+    h = F.relu(F.linear(h, w["output_layers.2.weight"], w["output_layers.2.bias"]))
+    return F.linear(h, w["output_layers.4.weight"], w["output_layers.4.bias"])
+
+
+def dnsmos_raw(w: dict, row: torch.Tensor) -> torch.Tensor:
+    """[S, 3] float32 raw network outputs of one unpadded 1-D row (two segments at a time)."""
+    segs = dnsmos_row_segments(row)
+    with torch.no_grad():
+        return torch.cat([dnsmos_network(w, dnsmos_features(w, segs[i:i + 2])) for i in range(0, segs.shape[0], 2)])
+
+
+def dnsmos(w: dict, rows: torch.Tensor, lengths=None) -> torch.Tensor:
+    """[B, 3] float32 (SIG, BAK, OVRL) of [B, L] rows; NaN for a row of no samples and for a row
+    with a non-finite sample among those its segments read."""
+    B, L = rows.shape
+    c0, c1, c2 = (torch.tensor(c, dtype=torch.float32) for c in _DNSMOS_POLY)
+
+    def one(b):
+        n = L if lengths is None else int(lengths[b])
+        row = rows[b, :n]
+        S = dnsmos_segments(n)
+        used = n if n <= DNSMOS_SEGMENT else DNSMOS_HOP * (S - 1) + DNSMOS_SEGMENT
+        if n < 1 or not bool(torch.isfinite(row[:used]).all()):
+            return torch.full((1, 3), float("nan"), dtype=torch.float32)
+        raw = dnsmos_raw(w, row)
+        poly = c0 + c1 * raw + c2 * raw.square()
+        return poly.double().mean(0, keepdim=True).float()
+
+    return torch.cat(_host_map(one, range(B))) if B else torch.empty(0, 3, dtype=torch.float32)

@@ -27,12 +27,14 @@ FSEM_ERATE = -5
 COMPOSITE_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_composite.so")
 LSD_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_lsd.so")
 BSSSDR_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_bsssdr.so")
+DNSMOS_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_dnsmos.so")
 
 _lock = threading.Lock()
 _lib = None
 _composite_lib = None
 _lsd_lib = None
 _bsssdr_lib = None
+_dnsmos_lib = None
 
 _c_i64 = ctypes.c_int64
 _c_i32 = ctypes.c_int32
@@ -111,6 +113,20 @@ BSSSDR_SIGNATURES = {
     "fsem_bsssdr_load_diag_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, ctypes.c_double, _vp, _vp,
                                                  _c_sz, _vp]),
 }
+# every symbol include/fsem_dnsmos.h declares (libfsem_dnsmos.so)
+_DNSMOS_RUN = (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_sz, _vp])
+DNSMOS_SIGNATURES = {
+    "fsem_dnsmos_segments": (_c_i64, [_c_i64]),
+    "fsem_dnsmos_weights_bytes": (_c_sz, []),
+    "fsem_dnsmos_pack_weights_f32": (ctypes.c_int, [_vp, _vp, _c_sz, _vp]),
+    "fsem_dnsmos_min_workspace_bytes": (_c_sz, []),
+    "fsem_dnsmos_workspace_bytes": (_c_sz, [_c_i64, _c_i64]),
+    "fsem_dnsmos_f32": _DNSMOS_RUN,
+    "fsem_dnsmos_features_f32": _DNSMOS_RUN,
+    "fsem_dnsmos_raw_f32": _DNSMOS_RUN,
+}
+DNSMOS_NUM_TENSORS = 22  # include/fsem_dnsmos.h FSEM_DNSMOS_NUM_TENSORS
+DNSMOS_MAX_PASS = 16  # include/fsem_dnsmos.h FSEM_DNSMOS_MAX_PASS
 ALIGN_MAX_SEGMENTS = 32  # include/fsem.h FSEM_ALIGN_MAX_SEGMENTS
 PESQ_MAX_BAD = 16  # include/fsem.h FSEM_PESQ_MAX_BAD
 
@@ -449,6 +465,39 @@ def load_bsssdr() -> ctypes.CDLL:
                 fn.argtypes = args
             _bsssdr_lib = lib
     return _bsssdr_lib
+
+
+def load_dnsmos() -> ctypes.CDLL:
+    """Load (once) and return libfsem_dnsmos.so (include/fsem_dnsmos.h), after libfsem.so (one HIP
+    runtime, one staleness check); raises if it is missing, built for another target or not the build
+    of this tree's sources."""
+    global _dnsmos_lib
+    if _dnsmos_lib is not None:
+        return _dnsmos_lib
+    load()
+    with _lock:
+        if _dnsmos_lib is None:
+            if not os.path.exists(DNSMOS_LIB_PATH):
+                raise ImportError(
+                    f"fsem DNSMOS engine not built: {DNSMOS_LIB_PATH} is missing "
+                    "(run `python -m fast_speech_enhancement_metrics_amd._build`)")
+            from . import _build
+            if all(os.path.exists(d) for d in _build.deps()):
+                have, want = _build.library_build_id(DNSMOS_LIB_PATH), _build.source_hash()
+                if have != want:
+                    raise ImportError(f"fsem DNSMOS engine {DNSMOS_LIB_PATH} is stale (build id {have}, sources "
+                                      f"{want}): rebuild it with `python -m fast_speech_enhancement_metrics_amd._build`")
+                arch = _build.library_build_arch(DNSMOS_LIB_PATH)
+                if arch != _build.ARCH:
+                    raise ImportError(f"fsem DNSMOS engine {DNSMOS_LIB_PATH} was built for {arch}, this process "
+                                      f"targets {_build.ARCH} (FSEM_OFFLOAD_ARCH)")
+            lib = ctypes.CDLL(DNSMOS_LIB_PATH, mode=ctypes.RTLD_LOCAL)
+            for name, (res, args) in DNSMOS_SIGNATURES.items():
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
+            _dnsmos_lib = lib
+    return _dnsmos_lib
 
 
 def check(rc: int, what: str) -> None:
