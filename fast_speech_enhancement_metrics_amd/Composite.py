@@ -16,7 +16,7 @@ from __future__ import annotations
 import torch
 
 from . import _cpu, _native
-from .base import BaseMetric, as_rows, device_lengths, noisy_shape, same_device
+from .base import BaseMetric, device_lengths, engine_rows, noisy_shape, pair_rows
 
 
 class Composite(BaseMetric):
@@ -48,11 +48,7 @@ class Composite(BaseMetric):
 
     def _rows_scores(self, clean_speech, denoised_speech, lengths):
         """The seven [B] score tensors of rows on their own device (one engine call)."""
-        clean = as_rows(clean_speech)
-        noisy = as_rows(denoised_speech)
-        if noisy.shape != clean.shape:
-            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
-        same_device(clean, noisy)
+        clean, noisy = pair_rows(clean_speech, denoised_speech)
         B, L = clean.shape
         sr = self.sample_rate
         if lengths is None and _cpu.pesq_frames(L * (16000 // sr)) < 20:
@@ -67,13 +63,8 @@ class Composite(BaseMetric):
                 out = _cpu.rows_parallel(lambda c, n: _cpu.composite(c, n, sr), clean, noisy)
             return tuple(v.to(torch.float32) for v in out)
         lib = _native.load_composite()
-        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
-        if clean.stride(0) != noisy.stride(0) or L % 4 or clean.stride(0) % 4 or \
-                (clean.data_ptr() | noisy.data_ptr()) % 16:
-            # the PESQ stage reads rows in 16-byte pieces, up to ceil4(L) floats (include/fsem.h)
-            pad = (-L) % 4
-            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-            noisy = torch.nn.functional.pad(noisy, (0, pad)).contiguous()
+        # (the PESQ stage reads rows in 16-byte pieces)
+        clean, noisy, L, lens = engine_rows(clean, noisy, lengths, aligned16=True)
         out = torch.empty(7, B, dtype=torch.float32, device=clean.device)
         if L == 0:  # (no samples in any row: nothing to launch)
             return tuple(out.fill_(float("nan")))
@@ -85,14 +76,9 @@ class Composite(BaseMetric):
         _native.check(rc, "Composite")
         return tuple(out[k] for k in range(7))
 
-    def _finish(self, *cols: torch.Tensor) -> list[dict[str, float]]:
-        t = torch.stack([c.float() for c in cols])
-        if t.is_cuda:  # the dicts are built while the GPU computes, then filled
-            return _native.list_from_device(self, t, self.KEYS)[0]
-        return _native.score_list(t, self.KEYS)
-
     def compute_metric(self, clean_speech: torch.Tensor | None, denoised_speech: torch.Tensor,
                        lengths=None) -> list[dict[str, float]]:
         assert clean_speech is not None
         with torch.no_grad():
-            return self._finish(*self.scores(clean_speech, denoised_speech, lengths=lengths))
+            cols = self.scores(clean_speech, denoised_speech, lengths=lengths)
+            return self.result_list(torch.stack([c.float() for c in cols]))

@@ -171,7 +171,4 @@ class DNSMOS(BaseMetric):
             raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
         with torch.no_grad():
             s = self.scores(denoised_speech, self.EXPECTED_SAMPLING_RATE, lengths=lengths)
-            t = s.float().t().contiguous()  # [3, B]
-            if t.is_cuda:  # the dicts are built while the GPU computes, then filled
-                return _native.list_from_device(self, t, self.KEYS)[0]
-            return _native.score_list(t, self.KEYS)
+            return self.result_list(s.float().t().contiguous())  # [3, B]

@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from . import _cpu, _native
-from .base import (BaseMetric, as_rows, check_row_rate, device_lengths, noisy_shape, resample_rows, same_device)
+from .base import (BaseMetric, check_row_rate, device_lengths, engine_rows, noisy_shape, pair_rows, resample_rows)
 
 
 class LSD(BaseMetric):
@@ -60,26 +60,15 @@ class LSD(BaseMetric):
         if sr != self.EXPECTED_SAMPLING_RATE:
             clean_speech, denoised_speech, lengths = resample_rows(clean_speech, denoised_speech, lengths, sr,
                                                                    self.EXPECTED_SAMPLING_RATE)
-        clean = as_rows(clean_speech)
-        noisy = as_rows(denoised_speech)
-        if noisy.shape != clean.shape:
-            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
-        same_device(clean, noisy)
+        clean, noisy = pair_rows(clean_speech, denoised_speech)
         B, L = clean.shape
         if not clean.is_cuda:
             if lengths is not None:
                 return _cpu.per_row(_cpu.lsd, clean, noisy, device_lengths(lengths, B, L, "cpu"))
             return _cpu.rows_parallel(_cpu.lsd, clean, noisy)
         lib = _native.load_lsd()
-        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
-        if L == 0:  # (the engine takes rows of at least one sample: one zero sample, no length)
-            clean, noisy, L = clean.new_zeros(B, 4), noisy.new_zeros(B, 4), 4
-            lens = torch.zeros(B, dtype=torch.int32, device=clean.device)
-        if clean.stride(0) != noisy.stride(0) or L % 4:
-            # rows must be readable up to ceil4(L) floats (include/fsem.h): pad odd lengths
-            pad = (-L) % 4
-            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-            noisy = torch.nn.functional.pad(noisy, (0, pad)).contiguous()
+        # (the engine takes rows of at least one sample: a row of none is zero samples of length 0)
+        clean, noisy, L, lens = engine_rows(clean, noisy, lengths, empty_as_zeros=True)
         out = torch.empty(B, dtype=torch.float32, device=clean.device)
         if B == 0:
             return out
@@ -95,7 +84,4 @@ class LSD(BaseMetric):
         assert clean_speech is not None
         with torch.no_grad():
             lsd = self.scores(clean_speech, denoised_speech, self.EXPECTED_SAMPLING_RATE, lengths=lengths)
-            t = lsd.float().reshape(1, -1)
-            if t.is_cuda:  # the dicts are built while the GPU computes, then filled
-                return _native.list_from_device(self, t, self.KEYS)[0]
-            return _native.score_list(t, self.KEYS)
+            return self.result_list(lsd.float().reshape(1, -1))

@@ -1,4 +1,4 @@
-"""Build libfsem.so (the gfx950 HIP engine) in-tree with hipcc.
+"""Build the gfx950 HIP engine's libraries (LIBRARIES) in-tree with hipcc.
 
     python -m fast_speech_enhancement_metrics_amd._build
 
@@ -14,11 +14,11 @@ import shutil
 import subprocess
 import sys
 import sysconfig
+from typing import NamedTuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
-LIB = os.path.join(LIBDIR, "libfsem.so")
 STAMP_LIB = os.path.join(LIBDIR, "libfsem_stamps.so")  # diagnostic build (tools/stamps.py)
 SOURCES = ["pesq.hip", "pesq_back.hip", "stoi.hip", "resample.hip", "align.hip", "sdr.hip", "runtime.hip"]
 # per-source code-generation flags: the STOI kernels and the resamplers are scheduled for ILP
@@ -38,24 +38,35 @@ SOURCE_FLAGS = {"pesq.hip": ["-fno-slp-vectorize"], "stoi.hip": _ILP, "resample.
 HEADERS = ["fsem_common.h", "fsem_fft.h", "fsem_internal.h", "fsem_pesq.h", "fsem_resample.h", "fsem_tables.inc",
            "fsem_vad.h"]
 HEADER_ABI = os.path.join(PKG, "..", "include", "fsem.h")
-# the Composite metric's engine: a library of its own that links against libfsem.so (whose entry
-# set is pinned entry by entry); built with it, from the same content hash
-COMPOSITE_LIB = os.path.join(LIBDIR, "libfsem_composite.so")
-COMPOSITE_SOURCES = ["composite.hip"]
 COMPOSITE_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_composite.h")
-# the LSD metric's engine: a third library, for the same reason; it uses fsem_common.h (the Arena,
-# the launch helpers) and none of libfsem.so's symbols, so it links alone
-LSD_LIB = os.path.join(LIBDIR, "libfsem_lsd.so")
-LSD_SOURCES = ["lsd.hip"]
 LSD_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_lsd.h")
-# the BSSSDR metric's engine (the reference's SDR): a fourth library, as libfsem_lsd.so
-BSSSDR_LIB = os.path.join(LIBDIR, "libfsem_bsssdr.so")
-BSSSDR_SOURCES = ["bsssdr.hip"]
 BSSSDR_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_bsssdr.h")
-# the DNSMOS metric's engine (f16 MFMA convolutions): a fifth library, as libfsem_lsd.so
-DNSMOS_LIB = os.path.join(LIBDIR, "libfsem_dnsmos.so")
-DNSMOS_SOURCES = ["dnsmos.hip"]
 DNSMOS_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_dnsmos.h")
+
+
+class Library(NamedTuple):
+    name: str  # the key of its binding table (_native.LIBRARY_SIGNATURES)
+    label: str  # what the loader's error messages call it ("fsem LSD engine ...")
+    file: str  # in LIBDIR
+    sources: list  # file names in CSRC (joined with it when used, not here)
+    header: str  # the module constant that holds its ABI header's path (read when used)
+    links_core: bool = False  # links against libfsem.so, found next to it at load time
+
+
+# every library of the package, in build order, all built from one content hash.  Each metric
+# after the core has a library of its own (libfsem.so's entry set is pinned entry by entry); they
+# use fsem_common.h (the Arena, the launch helpers) and link alone, except Composite's, whose
+# PESQ stage calls into libfsem.so.  A further library is one more entry here, a binding table in
+# _native, its header and its source.
+LIBRARIES = (
+    Library("core", "HIP", "libfsem.so", SOURCES, "HEADER_ABI"),
+    Library("composite", "Composite", "libfsem_composite.so", ["composite.hip"], "COMPOSITE_HEADER_ABI",
+            links_core=True),
+    Library("lsd", "LSD", "libfsem_lsd.so", ["lsd.hip"], "LSD_HEADER_ABI"),
+    Library("bsssdr", "BSSSDR", "libfsem_bsssdr.so", ["bsssdr.hip"], "BSSSDR_HEADER_ABI"),
+    Library("dnsmos", "DNSMOS", "libfsem_dnsmos.so", ["dnsmos.hip"], "DNSMOS_HEADER_ABI"),
+)
+LIB, COMPOSITE_LIB, LSD_LIB, BSSSDR_LIB, DNSMOS_LIB = (os.path.join(LIBDIR, _l.file) for _l in LIBRARIES)
 ARCH = os.environ.get("FSEM_OFFLOAD_ARCH", "gfx950")
 # code-generation flags; the target (--offload-arch=ARCH) is added at build time and recorded in
 # the library on its own (FSEM_BUILD_ARCH): a library built for another target is refused at
@@ -76,11 +87,27 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found: the fsem HIP engine cannot be built")
 
 
+def library(name: str) -> Library:
+    for lib in LIBRARIES:
+        if lib.name == name:
+            return lib
+    raise KeyError(f"no library {name!r} (_build.LIBRARIES)")
+
+
+def library_path(lib: Library) -> str:
+    return os.path.join(LIBDIR, lib.file)
+
+
+def header_abi(lib: Library) -> str:
+    return globals()[lib.header]
+
+
 def deps() -> list:
-    """Every file whose content the library depends on."""
-    return [os.path.join(CSRC, f) for f in SOURCES + HEADERS + COMPOSITE_SOURCES + LSD_SOURCES +
-                                         BSSSDR_SOURCES + DNSMOS_SOURCES] + \
-           [HEADER_ABI, COMPOSITE_HEADER_ABI, LSD_HEADER_ABI, BSSSDR_HEADER_ABI, DNSMOS_HEADER_ABI]
+    """Every file whose content the libraries depend on: the core's sources, the shared headers,
+    the other libraries' sources, then each library's ABI header."""
+    core, *engines = LIBRARIES
+    names = core.sources + HEADERS + [src for lib in engines for src in lib.sources]
+    return [os.path.join(CSRC, f) for f in names] + [header_abi(lib) for lib in LIBRARIES]
 
 
 def source_hash() -> str:
@@ -120,19 +147,29 @@ def library_build_arch(path: str = LIB):
 
 
 def _stale() -> bool:
-    """True when libfsem.so is missing or was built from other sources or flags than the tree's
+    """True when a library is missing or was built from other sources or flags than the tree's
     (content hash: an edited header or a changed SOURCE_FLAGS entry rebuilds; a touched file
     whose content is unchanged does not), or for another target than ARCH."""
     want = source_hash()
-    return library_build_id(LIB) != want or library_build_arch(LIB) != ARCH or \
-        library_build_id(COMPOSITE_LIB) != want or library_build_id(LSD_LIB) != want or \
-        library_build_arch(LSD_LIB) != ARCH or library_build_id(BSSSDR_LIB) != want or \
-        library_build_arch(BSSSDR_LIB) != ARCH or library_build_id(DNSMOS_LIB) != want or \
-        library_build_arch(DNSMOS_LIB) != ARCH
+    return any(library_build_id(path) != want or library_build_arch(path) != ARCH
+               for path in map(library_path, LIBRARIES))
+
+
+def _object(objdir: str, src: str) -> str:
+    return os.path.join(objdir, src.replace(".hip", ".o"))
+
+
+def _link(out: str, objs: list, extra: list, verbose: bool) -> None:
+    """Link `objs` into a per-process temporary file, then replace `out` with it atomically."""
+    tmp = f"{out}.{os.getpid()}.tmp"
+    cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + objs + extra
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=CSRC)
+    os.replace(tmp, out)
 
 
 def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> str:
-    lib = STAMP_LIB if stamps else LIB
     if not force and not stamps and not _stale():
         return LIB
     os.makedirs(LIBDIR, exist_ok=True)
@@ -143,64 +180,24 @@ def build(force: bool = False, verbose: bool = False, stamps: bool = False) -> s
     base = [_hipcc()] + BASE_FLAGS + [f'-DFSEM_BUILD_ID="{source_hash()}"', f'-DFSEM_BUILD_ARCH="{ARCH}"']
     if stamps:
         base.append("-DFSEM_STAMPS")
-    objs = []
+    libs = LIBRARIES[:1] if stamps else LIBRARIES  # (the diagnostic build: the core alone, into STAMP_LIB)
     try:
         procs = []
-        for src in SOURCES + ([] if stamps else COMPOSITE_SOURCES + LSD_SOURCES + BSSSDR_SOURCES +
-                                   DNSMOS_SOURCES):  # one object per source (per-source flags, compiled in parallel), one library
-            obj = os.path.join(objdir, src.replace(".hip", ".o"))
-            cmd = base + SOURCE_FLAGS.get(src, []) + ["-c", "-o", obj, os.path.join(CSRC, src)]
+        for src in [src for lib in libs for src in lib.sources]:
+            # one object per source (per-source flags, compiled in parallel)
+            cmd = base + SOURCE_FLAGS.get(src, []) + ["-c", "-o", _object(objdir, src), os.path.join(CSRC, src)]
             if verbose:
                 print(" ".join(cmd))
             procs.append((subprocess.Popen(cmd, cwd=CSRC), cmd))
-            objs.append(obj)
         for p, cmd in procs:
             if p.wait() != 0:
                 raise subprocess.CalledProcessError(p.returncode, cmd)
-        cobjs = [] if stamps else objs[len(SOURCES):len(SOURCES) + len(COMPOSITE_SOURCES)]
-        nl = len(SOURCES) + len(COMPOSITE_SOURCES)
-        lobjs = [] if stamps else objs[nl:nl + len(LSD_SOURCES)]
-        nb = nl + len(LSD_SOURCES)
-        bobjs = [] if stamps else objs[nb:nb + len(BSSSDR_SOURCES)]
-        dobjs = [] if stamps else objs[nb + len(BSSSDR_SOURCES):]
-        tmp = f"{lib}.{os.getpid()}.tmp"
-        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + objs[:len(SOURCES)]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd, cwd=CSRC)
-        os.replace(tmp, lib)
-        if cobjs:  # libfsem_composite.so needs libfsem.so, found next to it at load time
-            tmp = f"{COMPOSITE_LIB}.{os.getpid()}.tmp"
-            cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + cobjs + \
-                  [f"-L{LIBDIR}", "-lfsem", "-Wl,-rpath,$ORIGIN"]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd, cwd=CSRC)
-            os.replace(tmp, COMPOSITE_LIB)
-        if lobjs:  # libfsem_lsd.so stands alone (no symbol of libfsem.so)
-            tmp = f"{LSD_LIB}.{os.getpid()}.tmp"
-            cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + lobjs
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd, cwd=CSRC)
-            os.replace(tmp, LSD_LIB)
-        if bobjs:  # libfsem_bsssdr.so stands alone too
-            tmp = f"{BSSSDR_LIB}.{os.getpid()}.tmp"
-            cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + bobjs
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd, cwd=CSRC)
-            os.replace(tmp, BSSSDR_LIB)
-        if dobjs:  # libfsem_dnsmos.so stands alone too
-            tmp = f"{DNSMOS_LIB}.{os.getpid()}.tmp"
-            cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", tmp] + dobjs
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd, cwd=CSRC)
-            os.replace(tmp, DNSMOS_LIB)
+        for lib in libs:
+            _link(STAMP_LIB if stamps else library_path(lib), [_object(objdir, src) for src in lib.sources],
+                  [f"-L{LIBDIR}", "-lfsem", "-Wl,-rpath,$ORIGIN"] if lib.links_core else [], verbose)
     finally:
         shutil.rmtree(objdir, ignore_errors=True)
-    return lib
+    return STAMP_LIB if stamps else LIB
 
 
 def build_score_list(force: bool = False, verbose: bool = False) -> str:

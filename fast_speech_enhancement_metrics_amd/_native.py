@@ -13,8 +13,9 @@ import threading
 
 import torch
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_DEFAULT_LIB = os.path.join(_PKG, "lib", "libfsem.so")
+from . import _build
+
+_DEFAULT_LIB = _build.LIB
 LIB_PATH = os.environ.get("FSEM_LIB", _DEFAULT_LIB)
 
 FSEM_OK = 0
@@ -24,17 +25,14 @@ FSEM_ELAUNCH = -3
 FSEM_ESHORT = -4
 FSEM_ERATE = -5
 
-COMPOSITE_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_composite.so")
-LSD_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_lsd.so")
-BSSSDR_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_bsssdr.so")
-DNSMOS_LIB_PATH = os.path.join(_PKG, "lib", "libfsem_dnsmos.so")
+COMPOSITE_LIB_PATH = _build.COMPOSITE_LIB
+LSD_LIB_PATH = _build.LSD_LIB
+BSSSDR_LIB_PATH = _build.BSSSDR_LIB
+DNSMOS_LIB_PATH = _build.DNSMOS_LIB
 
 _lock = threading.Lock()
 _lib = None
-_composite_lib = None
-_lsd_lib = None
-_bsssdr_lib = None
-_dnsmos_lib = None
+_engines = {}  # name -> loaded library (load_engine)
 
 _c_i64 = ctypes.c_int64
 _c_i32 = ctypes.c_int32
@@ -125,6 +123,9 @@ DNSMOS_SIGNATURES = {
     "fsem_dnsmos_features_f32": _DNSMOS_RUN,
     "fsem_dnsmos_raw_f32": _DNSMOS_RUN,
 }
+# one binding table per library of _build.LIBRARIES, by its name there
+LIBRARY_SIGNATURES = {"core": SIGNATURES, "composite": COMPOSITE_SIGNATURES, "lsd": LSD_SIGNATURES,
+                      "bsssdr": BSSSDR_SIGNATURES, "dnsmos": DNSMOS_SIGNATURES}
 DNSMOS_NUM_TENSORS = 22  # include/fsem_dnsmos.h FSEM_DNSMOS_NUM_TENSORS
 DNSMOS_MAX_PASS = 16  # include/fsem_dnsmos.h FSEM_DNSMOS_MAX_PASS
 ALIGN_MAX_SEGMENTS = 32  # include/fsem.h FSEM_ALIGN_MAX_SEGMENTS
@@ -165,7 +166,6 @@ def _load_score_list():
                 import importlib.machinery
                 import importlib.util
 
-                from . import _build
                 path = _build.build_score_list()
                 loader = importlib.machinery.ExtensionFileLoader("_score_list", path)
                 spec = importlib.util.spec_from_file_location("_score_list", path, loader=loader)
@@ -333,7 +333,6 @@ def _check_build_id() -> None:
     variant chosen explicitly, tools/ab_*.py) is not checked."""
     if LIB_PATH != _DEFAULT_LIB:
         return
-    from . import _build
     if not all(os.path.exists(d) for d in _build.deps()):
         return  # no source tree next to the package (nothing to compare with)
     arch = _build.library_build_arch(LIB_PATH)
@@ -383,121 +382,56 @@ def load() -> ctypes.CDLL:
     return _lib
 
 
-def load_composite() -> ctypes.CDLL:
-    """Load (once) and return libfsem_composite.so (include/fsem_composite.h), after libfsem.so,
-    which it links against; raises if it is missing or not the build of this tree's sources."""
-    global _composite_lib
-    if _composite_lib is not None:
-        return _composite_lib
+def load_engine(name: str) -> ctypes.CDLL:
+    """Load (once) and return the library `name` of _build.LIBRARIES other than the core, after
+    libfsem.so (one HIP runtime, one staleness check; Composite's links against it); raises if it
+    is missing, not the build of this tree's sources or built for another target."""
+    lib = _engines.get(name)
+    if lib is not None:
+        return lib
     load()
     with _lock:
-        if _composite_lib is None:
-            if not os.path.exists(COMPOSITE_LIB_PATH):
+        if name not in _engines:
+            entry = _build.library(name)
+            if entry is _build.LIBRARIES[0]:
+                raise ValueError("load_engine: the core library has its own loader, load()")
+            path, what = _build.library_path(entry), f"fsem {entry.label} engine"
+            if not os.path.exists(path):
                 raise ImportError(
-                    f"fsem Composite engine not built: {COMPOSITE_LIB_PATH} is missing "
+                    f"{what} not built: {path} is missing "
                     "(run `python -m fast_speech_enhancement_metrics_amd._build`)")
-            from . import _build
             if all(os.path.exists(d) for d in _build.deps()):
-                have, want = _build.library_build_id(COMPOSITE_LIB_PATH), _build.source_hash()
+                have, want = _build.library_build_id(path), _build.source_hash()
                 if have != want:
-                    raise ImportError(f"fsem Composite engine {COMPOSITE_LIB_PATH} is stale (build id {have}, sources "
+                    raise ImportError(f"{what} {path} is stale (build id {have}, sources "
                                       f"{want}): rebuild it with `python -m fast_speech_enhancement_metrics_amd._build`")
-            lib = ctypes.CDLL(COMPOSITE_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-            for name, (res, args) in COMPOSITE_SIGNATURES.items():
-                fn = getattr(lib, name)
+            arch = _build.library_build_arch(path)
+            if arch != _build.ARCH:
+                raise ImportError(f"{what} {path} was built for {arch}, this process "
+                                  f"targets {_build.ARCH} (FSEM_OFFLOAD_ARCH)")
+            lib = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+            for fname, (res, args) in LIBRARY_SIGNATURES[name].items():
+                fn = getattr(lib, fname)
                 fn.restype = res
                 fn.argtypes = args
-            _composite_lib = lib
-    return _composite_lib
+            _engines[name] = lib
+    return _engines[name]
+
+
+def load_composite() -> ctypes.CDLL:
+    return load_engine("composite")  # libfsem_composite.so (include/fsem_composite.h)
 
 
 def load_lsd() -> ctypes.CDLL:
-    """Load (once) and return libfsem_lsd.so (include/fsem_lsd.h), after libfsem.so (one HIP runtime,
-    one staleness check); raises if it is missing or not the build of this tree's sources."""
-    global _lsd_lib
-    if _lsd_lib is not None:
-        return _lsd_lib
-    load()
-    with _lock:
-        if _lsd_lib is None:
-            if not os.path.exists(LSD_LIB_PATH):
-                raise ImportError(
-                    f"fsem LSD engine not built: {LSD_LIB_PATH} is missing "
-                    "(run `python -m fast_speech_enhancement_metrics_amd._build`)")
-            from . import _build
-            if all(os.path.exists(d) for d in _build.deps()):
-                have, want = _build.library_build_id(LSD_LIB_PATH), _build.source_hash()
-                if have != want:
-                    raise ImportError(f"fsem LSD engine {LSD_LIB_PATH} is stale (build id {have}, sources "
-                                      f"{want}): rebuild it with `python -m fast_speech_enhancement_metrics_amd._build`")
-            lib = ctypes.CDLL(LSD_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-            for name, (res, args) in LSD_SIGNATURES.items():
-                fn = getattr(lib, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lsd_lib = lib
-    return _lsd_lib
+    return load_engine("lsd")  # libfsem_lsd.so (include/fsem_lsd.h)
 
 
 def load_bsssdr() -> ctypes.CDLL:
-    """Load (once) and return libfsem_bsssdr.so (include/fsem_bsssdr.h), after libfsem.so (one HIP
-    runtime, one staleness check); raises if it is missing or not the build of this tree's sources."""
-    global _bsssdr_lib
-    if _bsssdr_lib is not None:
-        return _bsssdr_lib
-    load()
-    with _lock:
-        if _bsssdr_lib is None:
-            if not os.path.exists(BSSSDR_LIB_PATH):
-                raise ImportError(
-                    f"fsem BSSSDR engine not built: {BSSSDR_LIB_PATH} is missing "
-                    "(run `python -m fast_speech_enhancement_metrics_amd._build`)")
-            from . import _build
-            if all(os.path.exists(d) for d in _build.deps()):
-                have, want = _build.library_build_id(BSSSDR_LIB_PATH), _build.source_hash()
-                if have != want:
-                    raise ImportError(f"fsem BSSSDR engine {BSSSDR_LIB_PATH} is stale (build id {have}, sources "
-                                      f"{want}): rebuild it with `python -m fast_speech_enhancement_metrics_amd._build`")
-            lib = ctypes.CDLL(BSSSDR_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-            for name, (res, args) in BSSSDR_SIGNATURES.items():
-                fn = getattr(lib, name)
-                fn.restype = res
-                fn.argtypes = args
-            _bsssdr_lib = lib
-    return _bsssdr_lib
+    return load_engine("bsssdr")  # libfsem_bsssdr.so (include/fsem_bsssdr.h)
 
 
 def load_dnsmos() -> ctypes.CDLL:
-    """Load (once) and return libfsem_dnsmos.so (include/fsem_dnsmos.h), after libfsem.so (one HIP
-    runtime, one staleness check); raises if it is missing, built for another target or not the build
-    of this tree's sources."""
-    global _dnsmos_lib
-    if _dnsmos_lib is not None:
-        return _dnsmos_lib
-    load()
-    with _lock:
-        if _dnsmos_lib is None:
-            if not os.path.exists(DNSMOS_LIB_PATH):
-                raise ImportError(
-                    f"fsem DNSMOS engine not built: {DNSMOS_LIB_PATH} is missing "
-                    "(run `python -m fast_speech_enhancement_metrics_amd._build`)")
-            from . import _build
-            if all(os.path.exists(d) for d in _build.deps()):
-                have, want = _build.library_build_id(DNSMOS_LIB_PATH), _build.source_hash()
-                if have != want:
-                    raise ImportError(f"fsem DNSMOS engine {DNSMOS_LIB_PATH} is stale (build id {have}, sources "
-                                      f"{want}): rebuild it with `python -m fast_speech_enhancement_metrics_amd._build`")
-                arch = _build.library_build_arch(DNSMOS_LIB_PATH)
-                if arch != _build.ARCH:
-                    raise ImportError(f"fsem DNSMOS engine {DNSMOS_LIB_PATH} was built for {arch}, this process "
-                                      f"targets {_build.ARCH} (FSEM_OFFLOAD_ARCH)")
-            lib = ctypes.CDLL(DNSMOS_LIB_PATH, mode=ctypes.RTLD_LOCAL)
-            for name, (res, args) in DNSMOS_SIGNATURES.items():
-                fn = getattr(lib, name)
-                fn.restype = res
-                fn.argtypes = args
-            _dnsmos_lib = lib
-    return _dnsmos_lib
+    return load_engine("dnsmos")  # libfsem_dnsmos.so (include/fsem_dnsmos.h)
 
 
 def check(rc: int, what: str) -> None:

@@ -109,6 +109,12 @@ class BaseMetric(ABC):
         denoised_speech = self.prepare_audio(denoised_speech, lengths)
         return clean_speech, denoised_speech
 
+    def result_list(self, t: torch.Tensor) -> list[dict[str, float]]:
+        """The drop-in call's result, a dict over ``self.KEYS`` per row, from [K, B] float32 scores."""
+        if t.is_cuda:  # the dicts are built while the GPU computes, then filled
+            return _native.list_from_device(self, t, self.KEYS)[0]
+        return _native.score_list(t, self.KEYS)
+
     @abstractmethod
     def compute_metric(self, clean_speech: torch.Tensor | None, denoised_speech: torch.Tensor,
                        lengths: torch.Tensor | None = None) -> list[dict[str, float]]:
@@ -174,6 +180,39 @@ def as_rows(x: torch.Tensor) -> torch.Tensor:
     if x.dim() != 2 or x.stride(-1) != 1 or x.stride(0) < x.shape[1]:
         x = x.reshape(-1, x.shape[-1]).contiguous()
     return x
+
+
+def pair_rows(clean, noisy):
+    """(clean, noisy) as float32 [B, L] rows (as_rows) of one shape on one device."""
+    clean = as_rows(clean)
+    noisy = as_rows(noisy)
+    if noisy.shape != clean.shape:
+        raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
+    same_device(clean, noisy)
+    return clean, noisy
+
+
+def engine_rows(clean: torch.Tensor, noisy: torch.Tensor, lengths, *, empty_as_zeros: bool = False,
+                aligned16: bool = False):
+    """pair_rows' CUDA rows as an engine call takes them: (clean, noisy, L, lens) with one row
+    stride, every row readable up to ceil4(L) floats (include/fsem.h) and ``lengths`` validated
+    against the rows as given, as an int32 device array or None.
+
+    ``empty_as_zeros``: rows of no samples (L == 0) become four zero samples with zero lengths, for
+    the engines that score such rows; otherwise L == 0 comes back and the caller does not launch.
+    ``aligned16``: the row stride a multiple of 4 floats and both bases 16-byte aligned as well,
+    for an engine that reads rows in 16-byte pieces (Composite's PESQ stage)."""
+    B, L = clean.shape
+    lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
+    if L == 0 and empty_as_zeros:
+        clean, noisy, L = clean.new_zeros(B, 4), noisy.new_zeros(B, 4), 4
+        lens = torch.zeros(B, dtype=torch.int32, device=clean.device)
+    if clean.stride(0) != noisy.stride(0) or L % 4 or \
+            (aligned16 and (clean.stride(0) % 4 or (clean.data_ptr() | noisy.data_ptr()) % 16)):
+        pad = (-L) % 4
+        clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
+        noisy = torch.nn.functional.pad(noisy, (0, pad)).contiguous()
+    return clean, noisy, L, lens
 
 
 def noisy_shape(x) -> tuple:

@@ -7,8 +7,6 @@ import ctypes
 import json
 import os
 import pickle
-import re
-import subprocess
 import warnings
 
 import numpy as np
@@ -205,32 +203,6 @@ def test_copy_and_pickle():
 
 
 # ------------------------------------------------------------------ the C-ABI, host side
-def test_bsssdr_library_exports_what_its_header_declares(lib, blib):
-    """libfsem_bsssdr.so exports exactly the fsem_* symbols include/fsem_bsssdr.h declares, the
-    binding table lists the same, the other libraries export none of them, and it carries the
-    tree's build id."""
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    src = re.sub(r"/\*.*?\*/", "", open(_build.BSSSDR_HEADER_ABI).read(), flags=re.S)
-    decl = set(re.findall(r"\b(fsem_[a-z0-9_]+)\s*\(", src))
-    assert decl == {"fsem_bsssdr_filter_length", "fsem_bsssdr_chunk", "fsem_bsssdr_norm_chunk",
-                    "fsem_bsssdr_workspace_bytes", "fsem_bsssdr_f32", "fsem_bsssdr_load_diag_f32"}
-
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return set(re.findall(r" T (fsem_[a-z0-9_]+)", out))
-
-    assert exported(_native.BSSSDR_LIB_PATH) == decl == set(_native.BSSSDR_SIGNATURES)
-    for path, table in ((_native.LIB_PATH, _native.SIGNATURES),
-                        (_native.COMPOSITE_LIB_PATH, _native.COMPOSITE_SIGNATURES),
-                        (_native.LSD_LIB_PATH, _native.LSD_SIGNATURES)):
-        assert not exported(path) & decl and not set(table) & decl
-    names = {os.path.basename(d) for d in _build.deps()}
-    assert os.path.basename(_build.BSSSDR_HEADER_ABI) in names and "bsssdr.hip" in names
-    assert _build.library_build_id(_build.BSSSDR_LIB) == _build.source_hash() == _native.build_id()
-    assert _build.library_build_arch(_build.BSSSDR_LIB) == _build.ARCH
-    assert lib.fsem_version() == 11  # (libfsem.so is as it was)
-
-
 def test_abi_geometry(blib):
     assert blib.fsem_bsssdr_filter_length() == 512
     C, NC = blib.fsem_bsssdr_chunk(), blib.fsem_bsssdr_norm_chunk()

@@ -171,31 +171,6 @@ def test_abi_queries(lib, clib):
     assert lib.fsem_version() == 11  # (libfsem.so is as it was: the composite entries are a library of their own)
 
 
-def test_composite_library_exports_what_its_header_declares(lib, clib):
-    """libfsem_composite.so exports exactly the fsem_* symbols include/fsem_composite.h declares,
-    the binding table lists the same, libfsem.so exports none of them, and both libraries carry the
-    tree's build id."""
-    import os
-    import re
-    import subprocess
-
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    src = open(_build.COMPOSITE_HEADER_ABI).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    decl = set(re.findall(r"\b(fsem_[a-z0-9_]+)\s*\(", src))
-    assert decl == {"fsem_composite_chunk", "fsem_composite_workspace_bytes", "fsem_composite_f32"}
-
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return set(re.findall(r" T (fsem_[a-z0-9_]+)", out))
-
-    assert exported(_native.COMPOSITE_LIB_PATH) == decl == set(_native.COMPOSITE_SIGNATURES)
-    assert not exported(_native.LIB_PATH) & decl and not set(_native.SIGNATURES) & decl
-    assert os.path.basename(_build.COMPOSITE_HEADER_ABI) in {os.path.basename(d) for d in _build.deps()}
-    assert _build.library_build_id(_build.COMPOSITE_LIB) == _build.source_hash() == _native.build_id()
-    assert _build.library_build_arch(_build.COMPOSITE_LIB) == _build.ARCH
-
-
 PAIRS = [(1, 100), (1, 5376), (3, 40077), (7, 160000), (4096, 160000), (70000, 16000), (0, 160000)]
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "composite_workspace_bytes.json")
 

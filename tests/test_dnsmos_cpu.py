@@ -5,8 +5,6 @@ lookup) and the NaN rows."""
 import ctypes
 import json
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,9 +16,6 @@ from . import dnsmos_cases as dc
 from .test_workspace_cpu import PAIRS
 
 WS_GOLDEN = os.path.join(dc.GOLDEN, "dnsmos_workspace_bytes.json")
-ENTRIES = {"fsem_dnsmos_segments", "fsem_dnsmos_weights_bytes", "fsem_dnsmos_pack_weights_f32",
-           "fsem_dnsmos_min_workspace_bytes", "fsem_dnsmos_workspace_bytes", "fsem_dnsmos_f32",
-           "fsem_dnsmos_features_f32", "fsem_dnsmos_raw_f32"}
 
 
 @pytest.fixture(scope="module")
@@ -37,29 +32,6 @@ def metric():
 
 
 # ------------------------------------------------------------------ library and fixtures
-def test_library_exports_what_its_header_declares(dlib):
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    src = re.sub(r"/\*.*?\*/", "", open(_build.DNSMOS_HEADER_ABI).read(), flags=re.S)
-    decl = set(re.findall(r"\b(fsem_[a-z0-9_]+)\s*\(", src))
-    assert decl == ENTRIES
-
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return set(re.findall(r" T (fsem_[a-z0-9_]+)", out))
-
-    assert exported(_native.DNSMOS_LIB_PATH) == decl == set(_native.DNSMOS_SIGNATURES)
-    for path, table in ((_native.LIB_PATH, _native.SIGNATURES), (_native.LSD_LIB_PATH, _native.LSD_SIGNATURES),
-                        (_native.BSSSDR_LIB_PATH, _native.BSSSDR_SIGNATURES),
-                        (_native.COMPOSITE_LIB_PATH, _native.COMPOSITE_SIGNATURES)):
-        assert not exported(path) & decl and not set(table) & decl
-    names = {os.path.basename(d) for d in _build.deps()}
-    assert os.path.basename(_build.DNSMOS_HEADER_ABI) in names and "dnsmos.hip" in names
-    assert _build.library_build_id(_build.DNSMOS_LIB) == _build.source_hash() == _native.build_id()
-    assert _build.library_build_arch(_build.DNSMOS_LIB) == _build.ARCH
-    assert not _build._stale()
-    assert _native.load().fsem_version() == 11  # (libfsem.so is as it was)
-
-
 def record_workspace(dlib) -> dict:
     return {"dnsmos": [dlib.fsem_dnsmos_workspace_bytes(b, l) for b, l in PAIRS],
             "min": dlib.fsem_dnsmos_min_workspace_bytes(), "weights": dlib.fsem_dnsmos_weights_bytes()}

@@ -6,8 +6,6 @@ import ctypes
 import json
 import os
 import pickle
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -150,30 +148,6 @@ def test_copy_and_pickle():
 
 
 # ------------------------------------------------------------------ the C-ABI, host side
-def test_lsd_library_exports_what_its_header_declares(lib, llib):
-    """libfsem_lsd.so exports exactly the fsem_* symbols include/fsem_lsd.h declares, the binding
-    table lists the same, the other two libraries export none of them, and it carries the tree's
-    build id."""
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    src = re.sub(r"/\*.*?\*/", "", open(_build.LSD_HEADER_ABI).read(), flags=re.S)
-    decl = set(re.findall(r"\b(fsem_[a-z0-9_]+)\s*\(", src))
-    assert decl == {"fsem_lsd_frames", "fsem_lsd_chunk", "fsem_lsd_workspace_bytes", "fsem_lsd_f32"}
-
-    def exported(path):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        return set(re.findall(r" T (fsem_[a-z0-9_]+)", out))
-
-    assert exported(_native.LSD_LIB_PATH) == decl == set(_native.LSD_SIGNATURES)
-    for path, table in ((_native.LIB_PATH, _native.SIGNATURES),
-                        (_native.COMPOSITE_LIB_PATH, _native.COMPOSITE_SIGNATURES)):
-        assert not exported(path) & decl and not set(table) & decl
-    names = {os.path.basename(d) for d in _build.deps()}
-    assert os.path.basename(_build.LSD_HEADER_ABI) in names and "lsd.hip" in names
-    assert _build.library_build_id(_build.LSD_LIB) == _build.source_hash() == _native.build_id()
-    assert _build.library_build_arch(_build.LSD_LIB) == _build.ARCH
-    assert lib.fsem_version() == 11  # (libfsem.so is as it was)
-
-
 def test_abi_geometry(llib):
     C = llib.fsem_lsd_chunk()
     assert C > 0 and C % 256 == 0
