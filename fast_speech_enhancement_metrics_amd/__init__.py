@@ -9,6 +9,7 @@
     BSSSDR(sample_rate=16000, use_gpu=True)(clean, denoised) -> [{"SDR": ...}, ...]  (the reference's SDR)
     DNSMOS(sample_rate=16000, use_gpu=True)(None, denoised) -> [{"SIG", "BAK", "OVRL"}, ...]  (the reference's DNSMOS)
     Composite(16000, use_gpu=True)(clean, denoised)        -> [{"CSIG", "CBAK", "COVL", "PESQ", "LLR", "WSS", "SegSNR"}, ...]  (extension)
+    SpectralMeasures(16000, use_gpu=True)(clean, denoised) -> [{"fwSegSNR", "CD", "IS"}, ...]  (extension)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
 """
@@ -18,9 +19,10 @@ from .STOI import STOI
 from .joint import PESQ_STOI
 from .SDR import SDR
 from .Composite import Composite
+from .Spectral import SpectralMeasures
 from .LSD import LSD
 from .BSSSDR import BSSSDR
 from .DNSMOS import DNSMOS
 from .alignment import time_align
 
-__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "LSD", "BSSSDR", "DNSMOS", "time_align"]
+__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "SpectralMeasures", "LSD", "BSSSDR", "DNSMOS", "time_align"]

@@ -917,6 +917,74 @@ def composite(clean: torch.Tensor, noisy: torch.Tensor, sample_rate: int = 16000
     return tuple(torch.where(bad, nan, v) for v in (csig, cbak, covl, mos, llr, wss, seg))
 
 
+# ----------------------------------------------------------------------------- Spectral measures
+# fwSegSNR, CD and IS (Hu & Loizou's evaluation set; not in the reference; engine:
+# csrc/spectral.hip, definitions: include/fsem.h "Spectral"), float64, all frames of a chunk of rows
+# at once.  Composite's frames, window, LPC order and band filters.
+def spectral_frames(s: torch.Tensor, h: torch.Tensor, sample_rate: int) -> torch.Tensor:
+    """[3, B, F] float64 frame values (fwSegSNR_f, CD_f, IS_f) of [B, n] float64 rows, n >= win."""
+    hop, win = sdr_geometry(sample_rate)
+    P = composite_order(sample_rate)
+    nfft = 1 << (2 * win - 1).bit_length()
+    H = nfft // 2
+    t = torch.arange(1, win + 1, dtype=torch.float64, device=s.device)
+    w = 0.5 * (1 - torch.cos(2 * math.pi * t / (win + 1)))
+    fs = s.unfold(1, win, hop) * w
+    fh = h.unfold(1, win, hop) * w
+    Rs = torch.stack([(fs[..., :win - k] * fs[..., k:]).sum(-1) for k in range(P + 1)], -1)
+    Rh = torch.stack([(fh[..., :win - k] * fh[..., k:]).sum(-1) for k in range(P + 1)], -1)
+    As, Ah = _lpc(Rs, P), _lpc(Rh, P)
+    lag = (torch.arange(P + 1)[:, None] - torch.arange(P + 1)[None, :]).abs().to(s.device)
+    Ts, Th = Rs[..., lag], Rh[..., lag]  # [B, F, P + 1, P + 1]
+    quad = lambda A, Tm: torch.einsum("bfi,bfij,bfj->bf", A, Tm, A)  # noqa: E731
+    Es, Eh = quad(As, Ts), quad(Ah, Th)
+    is_f = (quad(Ah, Ts) / Eh + torch.log(Eh / Es) - 1).clamp(max=100)
+
+    def cepstrum(A):
+        c = [torch.zeros_like(A[..., 0])]
+        for m in range(1, P + 1):
+            acc = sum((k * c[k] * A[..., m - k] for k in range(1, m)), torch.zeros_like(A[..., 0]))
+            c.append(-A[..., m] - acc / m)
+        return torch.stack(c[1:], -1)
+
+    cd_f = (10 / math.log(10) * torch.sqrt(2 * (cepstrum(As) - cepstrum(Ah)).square().sum(-1))).clamp(max=10)
+    G = _wss_filters(int(sample_rate), nfft).to(s.device)
+
+    def band_sums(fr):
+        M = torch.fft.rfft(fr, nfft).abs()[..., :H]
+        tot = M.sum(-1, keepdim=True)
+        return torch.where(tot > 0, M / tot, torch.zeros_like(M)) @ G.T
+
+    es, eh = band_sums(fs), band_sums(fh)
+    err = (es - eh).square().clamp_min(2.0 ** -52)
+    W = es ** 0.2
+    on = W > 0
+    term = torch.where(on, W * 10 * torch.log10(torch.where(on, es.square() / err, torch.ones_like(es))),
+                       torch.zeros_like(W))
+    den = W.sum(-1)
+    fw_f = torch.where(den > 0, (term.sum(-1) / den).clamp(-10, 35), torch.full_like(den, float("nan")))
+    return torch.stack([fw_f, cd_f, is_f])
+
+
+def spectral(clean: torch.Tensor, noisy: torch.Tensor, sample_rate: int = 16000, return_frames: bool = False):
+    """[B, n] rows at ``sample_rate`` (8000 or 16000) -> (fwsegsnr, cd, is), [B] float64 each; with
+    ``return_frames`` also the [3, B, F] float64 frame values.  Torch ops on the rows' device."""
+    B, n = clean.shape
+    hop, win = sdr_geometry(sample_rate)
+    F = (n - win) // hop + 1 if n >= win else 0
+    nan = torch.full((B,), float("nan"), dtype=torch.float64, device=clean.device)
+    if F == 0 or B == 0:
+        out = (nan, nan.clone(), nan.clone())
+        return out + (torch.zeros(3, B, 0, dtype=torch.float64, device=clean.device),) if return_frames else out
+    s = clean.to(torch.float64)
+    h = noisy.to(torch.float64)
+    fr = torch.cat([spectral_frames(s[i:i + _COMPOSITE_ROWS], h[i:i + _COMPOSITE_ROWS], sample_rate)
+                    for i in range(0, B, _COMPOSITE_ROWS)], 1)
+    bad = ~(torch.isfinite(s).all(1) & torch.isfinite(h).all(1))
+    out = tuple(torch.where(bad, nan, v) for v in (fr[0].mean(1), _trimmed_mean(fr[1]), _trimmed_mean(fr[2])))
+    return out + (fr,) if return_frames else out
+
+
 # ----------------------------------------------------------------------------- DNSMOS
 # The reference's DNSMOS network (DNSMOS.py) in float32 torch ops from the checkpoint's tensors
 # (a dict of state-dict names -> float32 CPU tensors); engine: csrc/dnsmos.hip.

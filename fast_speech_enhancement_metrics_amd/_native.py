@@ -86,6 +86,9 @@ SIGNATURES = {
     "fsem_sdr_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i32]),
     "fsem_sdr_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp, _vp, _vp, _vp,
                                      _c_sz, _vp]),
+    "fsem_spectral_order": (ctypes.c_int, [_c_i32]),
+    "fsem_spectral_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _vp,
+                                          _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

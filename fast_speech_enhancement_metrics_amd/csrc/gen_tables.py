@@ -128,6 +128,41 @@ def scan_tables(M, K, ch):
     return G, A
 
 
+SPEC_GW, SPEC_GO = 32, 15  # bins per band in the sparse filter table; its first bin is f0 - SPEC_GO
+SPEC_CENTRE = (50.0, 120.0, 190.0, 260.0, 330.0, 400.0, 470.0, 540.0, 617.372, 703.378, 798.717, 904.128, 1020.38,
+               1148.30, 1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17,
+               3597.63)
+SPEC_WIDTH = (70.0,) * 7 + (77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914, 140.423, 153.823, 168.154, 183.457,
+                            199.776, 217.153, 235.631, 255.255, 276.072, 298.126, 321.465, 346.136)
+
+
+def spectral_tables(sr: int):
+    """(window [win], sparse filters [25, SPEC_GW], first bins [25]) of SpectralMeasures at `sr`, float64."""
+    hop = sr * 30 // 4000
+    win = 4 * hop
+    H = 256 if sr == 8000 else 512
+    half = sr / 2.0
+    t = np.arange(win, dtype=np.float64)
+    w = 0.5 * (1.0 - np.cos(2.0 * np.pi * (t + 1.0) / (win + 1.0)))
+    floor = np.exp(-30.0 / (2.0 * 2.303))
+    g = np.zeros((25, SPEC_GW))
+    j0 = np.zeros(25, dtype=np.int64)
+    for i, (c, b) in enumerate(zip(SPEC_CENTRE, SPEC_WIDTH)):
+        f0 = int(np.floor(c * H / half))
+        bw = b * H / half
+        j = np.arange(H)
+        full = np.exp(-11.0 * ((j - f0) / bw) ** 2 + np.log(SPEC_WIDTH[0]) - np.log(b))
+        full[full <= floor] = 0.0
+        j0[i] = f0 - SPEC_GO
+        for q in range(SPEC_GW):
+            if 0 <= j0[i] + q < H:
+                g[i, q] = full[j0[i] + q]
+        inside = np.zeros(H, dtype=bool)
+        inside[max(j0[i], 0):min(j0[i] + SPEC_GW, H)] = True
+        assert not full[~inside].any(), (sr, i)  # nothing of the filter lies outside the sparse window
+    return w, g, j0
+
+
 def main():
     from scipy.signal import butter
     import torch
@@ -268,6 +303,22 @@ def main():
     rk, width, orig, new = sinc_kernel(16000, 10000)
     assert (width, orig, new) == (10, 8, 5) and tuple(rk.shape) == (5, 28)
     lines.append(arr("kRs16k10k", rk.numpy()))
+
+    # SpectralMeasures (spectral.hip; include/fsem.h "Spectral"): per rate (8 kHz, 16 kHz) the frame
+    # window w[t] = 0.5 (1 - cos(2 pi (t + 1) / (win + 1))) and the 25 critical-band filters as a
+    # sparse table, SPEC_GW bins per band from bin f0_i - SPEC_GO (the filters are zero outside
+    # +-14 bins after the threshold; asserted); and the split-step twiddles W_1024^j of the
+    # 1024-point real transform.  The formulas of composite.hip's composite_tables.
+    lines.append(f"#define FSEM_SPEC_GW {SPEC_GW}")
+    lines.append(f"#define FSEM_SPEC_GO {SPEC_GO}")
+    for tag, sr in (("8k", 8000), ("16k", 16000)):
+        win, g, j0 = spectral_tables(sr)
+        lines.append(arr(f"kSpecWin{tag}", win, qual="__constant__ static const"))
+        lines.append(arr(f"kSpecG{tag}", g, qual="__constant__ static const"))
+        lines.append(arr(f"kSpecJ0{tag}", j0, "int", qual="__constant__ static const"))
+    j = np.arange(512)
+    lines.append(arr("kSpecTw", np.stack([np.cos(np.pi * j / 512), np.sin(np.pi * j / 512)], axis=1),
+                     qual="__constant__ static const"))
 
     out = os.path.join(HERE, "fsem_tables.inc")
     with open(out, "w") as fh:

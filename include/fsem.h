@@ -63,6 +63,8 @@ extern "C" {
 #define FSEM_ERATE -5         /* unsupported sample-rate pair (see resampling)      */
 
 const char *fsem_strerror(int code);
+/* (fsem_spectral_* joined at ABI 11 without a bump: entries that take no workspace add to the set
+ * and change no existing entry, workspace size or layout.) */
 int fsem_version(void);  /* 11: + fsem_sdr_*; 10: + fsem_pesq_wb_frames_f32; 9: + fsem_pesq_bad_intervals_*, fsem_pesq_pool_f32; 8: + fsem_time_align_p862_*; 7: + fsem_host_buffer_mapped; 6: + fsem_build_id; 5: + fsem_time_align_utt_*; 4: + fsem_pre_emphasize_f32; 3: time alignment, distances */
 /* Content hash (16 hex digits) of the sources, headers and compile flags this library was built
  * from (fast_speech_enhancement_metrics_amd/_build.py source_hash); the host layer refuses a
@@ -351,6 +353,82 @@ size_t fsem_sdr_workspace_bytes(int64_t batch, int64_t length, int32_t sample_ra
 int fsem_sdr_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
                  const int32_t *lengths, int32_t sample_rate, int32_t zero_mean, float *si_sdr, float *snr,
                  float *seg_snr, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------- Spectral: fwSegSNR, CD, IS
+ * (ABI 11: fsem_version() stays 11; these entries take no workspace and change no other entry.)
+ * Replaces nothing in the reference.  Three measures of Hu & Loizou's evaluation set per row pair:
+ * the frequency-weighted segmental SNR (fwSegSNR, dB), the LPC cepstral distance (CD, dB) and the
+ * Itakura-Saito distance (IS), with their per-frame values as a caller-provided output.  No
+ * implementation of Loizou's comp_fwseg.m, comp_cep.m and comp_is.m was available to compare with:
+ * agreement with them is by definition only.  0-based indices throughout.
+ *
+ * Shared with Composite.  Per row, s and s^ are the first n samples of the clean and the denoised
+ * row.  The window w, hop, win, the F complete frames, the LPC order P, nfft (512 or 1024),
+ * H = nfft / 2 and the 25 band filters g_i[j] with their threshold are exactly those of
+ * include/fsem_composite.h (frames: SegSNR's, F = fsem_sdr_frames(n, sample_rate)).
+ *
+ * LPC quantities.  As for LLR: R_x[k] = sum_t x[t] x[t + k] over the windowed frame,
+ * A_x = [1, a_1 ... a_P] from Levinson-Durbin on R_x, T_x the Toeplitz matrix of R_x.
+ *
+ * CD_f.
+ *  - Cepstrum of 1 / A(z): c[1] = -a[1]; c[m] = -a[m] - sum_{k=1}^{m-1} (k / m) c[k] a[m - k], m = 2 ... P.
+ *  - CD_f = min(10, (10 / ln 10) sqrt(2 sum_{m=1}^{P} (c_s[m] - c_s^[m])^2)).
+ *
+ * IS_f.
+ *  - E_x = A_x T_x A_x'.
+ *  - IS_f = min(100, (A_s^ T_s A_s^') / E_s^ + ln(E_s^ / E_s) - 1).
+ *
+ * NaN frames (CD, IS).  A frame with R[0] == 0 in either signal is NaN in CD_f and IS_f, by 0 / 0,
+ * as for LLR.
+ *
+ * fwSegSNR_f.
+ *  - M_x[j] = |FFT_nfft(frame)[j]|, j < H.
+ *  - m_x = M_x / sum_j M_x, or all zeros when that sum is 0.
+ *  - e_x[i] = sum_j m_x[j] g_i[j].
+ *  - err[i] = max((e_s[i] - e_s^[i])^2, 2^-52).
+ *  - W[i] = e_s[i]^0.2.
+ *  - v = sum_i W[i] 10 log10(e_s[i]^2 / err[i]) / sum_i W[i], over the bands with W[i] > 0.
+ *  - fwSegSNR_f = clamp(v, -10, 35); NaN when no band has W[i] > 0 (a digitally silent clean frame).
+ *
+ * Row values.
+ *  - CD and IS follow Composite's rule for LLR: the mean of the K = (19 F + 10) / 20 smallest frame
+ *    values, NaN sorted last; NaN when a NaN lies among the K or when F = 0.
+ *  - fwSegSNR is the mean of all F frame values; NaN when any frame is NaN or when F = 0.  A row kept
+ *    NaN by silent clean frames is a convention: callers can take their own mean of `frames`.
+ *  - A row holding a non-finite sample among its first n (also in the tail that no frame covers), or
+ *    a row of length 0, is NaN in all three scores; other rows are unaffected.  The row kernel scans
+ *    the row's samples itself.  The frame values of such a row are whatever the arithmetic gives.
+ *  - The reduction, for recomputing a score from `frames` bit for bit: thread t of 256 adds its
+ *    values v[t], v[t + 256], ... in that order in double -- for CD and IS only those below the
+ *    K-th smallest value x_K in the floats' order; the 256 sums are added by halving
+ *    (u[i] += u[i + h] for i < h; h = 128, 64 ... 1); CD and IS then add c x_K, c the number of
+ *    copies of x_K among the K smallest; the total is divided by K (fwSegSNR: F) in double and
+ *    rounded to float32.
+ *
+ * Precision.  The window product is float32.  The autocorrelation, Levinson-Durbin, the cepstrum,
+ * the quadratic forms, ln and sqrt are double.  The spectra, magnitudes, their normalisation and the
+ * band sums are float32.  The band log ratio and the weighted mean are double.  Frame values are
+ * stored as float32; the row sums are accumulated in double in the one order above.  Clean and
+ * denoised never share one complex transform (a silent frame has an exactly zero spectrum).
+ *   ref, deg : [batch, length] float32 (row stride ld >= length); read 4 bytes at a time, at any
+ *              alignment
+ *   lengths  : NULL or [batch] int32 per-row lengths (Conventions)
+ *   frames   : [3][batch][ldf] float32, required; plane k holds measure k (fwSegSNR, CD, IS): row b,
+ *              frame f at frames[(k * batch + b) * ldf + f]; ldf >= max(F, 1), F of `length`; with
+ *              `lengths`, the entries past a row's own F are left unwritten
+ *   fwsegsnr, cd, is_ : [batch] float32 outputs
+ * Null pointers, ldf < F, batch < 0, ld < length and rows past 2^29 samples give FSEM_EINVAL before
+ * any launch; sample_rate other than 8000 or 16000 gives FSEM_ERATE (fsem_spectral_order: 0).
+ * batch == 0 gives FSEM_OK with nothing launched; length == 0 gives FSEM_OK with no frame kernel
+ * launched and every score NaN.  No hidden device allocation, no workspace, no atomics whose order
+ * can change a result (integer histogram counts only).  A row's three scores and its frame values
+ * are bitwise the same whatever the batch size, the row's position, `length`, `ld`, `ldf` and the
+ * stream.
+ */
+int fsem_spectral_order(int32_t sample_rate);  /* LPC order P: 10 at 8000, 16 at 16000, 0 otherwise */
+int fsem_spectral_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                      const int32_t *lengths, int32_t sample_rate, float *frames, int64_t ldf, float *fwsegsnr,
+                      float *cd, float *is_, void *stream);
 
 #ifdef __cplusplus
 }
