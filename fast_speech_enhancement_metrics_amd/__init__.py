@@ -10,6 +10,7 @@
     DNSMOS(sample_rate=16000, use_gpu=True)(None, denoised) -> [{"SIG", "BAK", "OVRL"}, ...]  (the reference's DNSMOS)
     Composite(16000, use_gpu=True)(clean, denoised)        -> [{"CSIG", "CBAK", "COVL", "PESQ", "LLR", "WSS", "SegSNR"}, ...]  (extension)
     SpectralMeasures(16000, use_gpu=True)(clean, denoised) -> [{"fwSegSNR", "CD", "IS"}, ...]  (extension)
+    SRMR(sample_rate=16000, use_gpu=True)(None, denoised)   -> [{"SRMR": ...}, ...]  (extension, no reference signal)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
 """
@@ -23,6 +24,8 @@ from .Spectral import SpectralMeasures
 from .LSD import LSD
 from .BSSSDR import BSSSDR
 from .DNSMOS import DNSMOS
+from .SRMR import SRMR
 from .alignment import time_align
 
-__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "SpectralMeasures", "LSD", "BSSSDR", "DNSMOS", "time_align"]
+__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "SpectralMeasures", "LSD", "BSSSDR", "DNSMOS", "SRMR",
+           "time_align"]

@@ -985,6 +985,99 @@ def spectral(clean: torch.Tensor, noisy: torch.Tensor, sample_rate: int = 16000,
     return out + (fr,) if return_frames else out
 
 
+# ----------------------------------------------------------------------------- SRMR
+# The speech-to-reverberation modulation energy ratio (include/fsem.h "SRMR"; engine:
+# csrc/srmr.hip) in float64: scipy's lfilter for the gammatone's four first-order complex sections
+# and for the eight modulation biquads.
+SRMR_CHANNELS, SRMR_MODS = 23, 8
+_SRMR_EARQ, _SRMR_MINBW = 9.26449, 24.7
+
+
+def srmr_geometry(sample_rate: int):
+    """(hop, window) in samples: 64 ms and 256 ms."""
+    return math.ceil(0.064 * sample_rate), math.ceil(0.256 * sample_rate)
+
+
+@functools.lru_cache(maxsize=4)
+def _srmr_filters(sample_rate: int):
+    """(poles p_i, gains g_i, ERB(cf_i)) of the 23 channels (descending cf), the 8 modulation
+    filters' (b, a) and their lower band edges L_k."""
+    fs = float(sample_rate)
+    c = _SRMR_EARQ * _SRMR_MINBW
+    i = np.arange(1, SRMR_CHANNELS + 1)
+    cf = -c + np.exp(i * (np.log(125 + c) - np.log(fs / 2 + c)) / SRMR_CHANNELS) * (fs / 2 + c)
+    erb = cf / _SRMR_EARQ + _SRMR_MINBW
+    p = np.exp((-2 * np.pi * 1.019 * erb + 2j * np.pi * cf) / fs)
+
+    def G(q):
+        u = q * np.exp(-2j * np.pi * cf / fs)
+        return u * (1 + 4 * u + u * u) / (1 - u) ** 4
+
+    g = np.abs(G(p) + G(p.conj())) / 2
+    mcf = 4.0 * 32.0 ** (np.arange(SRMR_MODS) / 7.0)
+    W0 = np.tan(np.pi * mcf / fs)
+    B0 = W0 / 2
+    a = np.stack([1 + B0 + W0 ** 2, 2 * W0 ** 2 - 2, 1 - B0 + W0 ** 2], 1)
+    b = np.stack([B0, np.zeros_like(B0), -B0], 1)
+    return p, g, erb, b / a[:, :1], a / a[:, :1], mcf - B0 * fs / (2 * np.pi)
+
+
+def srmr_energies(x: np.ndarray, sample_rate: int) -> np.ndarray:
+    """A[i, k] of [B, n] float64 rows with at least one frame: [B, 23, 8]."""
+    wi, wl = srmr_geometry(sample_rate)
+    B, n = x.shape
+    F = (n - wl) // wi + 1
+    nend = (F - 1) * wi + wl
+    p, g, _, mb, ma, _ = _srmr_filters(sample_rate)
+    w2 = np.square(0.54 - 0.46 * np.cos(2 * np.pi * np.arange(wl) / wl))
+    V = np.zeros(nend)
+    for f in range(F):
+        V[f * wi:f * wi + wl] += w2
+    A = np.empty((B, SRMR_CHANNELS, SRMR_MODS))
+    for i in range(SRMR_CHANNELS):
+        y = lfilter(np.array([0, p[i], 4 * p[i] ** 2, p[i] ** 3]) / g[i], [1.0], x.astype(np.complex128), axis=-1)
+        for _ in range(4):
+            y = lfilter([1.0], [1.0, -p[i]], y, axis=-1)
+        e = np.abs(y)
+        for k in range(SRMR_MODS):
+            m = lfilter(mb[k], ma[k], e, axis=-1)[:, :nend]
+            A[:, i, k] = np.square(m) @ V / F
+    return A
+
+
+def srmr_score(A: np.ndarray, sample_rate: int) -> np.ndarray:
+    """SRMR of [B, 23, 8] energies: the 90 % bandwidth rule and the ratio."""
+    _, _, erb, _, _, L = _srmr_filters(sample_rate)
+    out = np.full(A.shape[0], np.nan)
+    for b in range(A.shape[0]):
+        ac = A[b].sum(1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            cum = np.cumsum(100 * ac[::-1] / ac.sum())
+            over = np.nonzero(cum > 90)[0]
+            bw = erb[SRMR_CHANNELS - 1 - over[0]] if len(over) else erb[0]
+            K = 8 if bw > L[7] else 7 if bw > L[6] else 6 if bw > L[5] else 5
+            out[b] = A[b, :, :4].sum() / A[b, :, 4:K].sum()
+    return out
+
+
+def srmr(rows: torch.Tensor, sample_rate: int = 16000, return_energies: bool = False):
+    """[B, n] rows at ``sample_rate`` (8000 or 16000) -> SRMR, [B] float64; with
+    ``return_energies`` also the [B, 23, 8] float64 energies A.  Rows without a frame or with a
+    non-finite sample are NaN."""
+    B, n = rows.shape
+    wi, wl = srmr_geometry(sample_rate)
+    score = torch.full((B,), float("nan"), dtype=torch.float64)
+    A = torch.full((B, SRMR_CHANNELS, SRMR_MODS), float("nan"), dtype=torch.float64)
+    if n >= wl and B:
+        x = rows.detach().to("cpu", torch.float64).numpy()
+        with np.errstate(invalid="ignore", over="ignore"):
+            a = srmr_energies(x, sample_rate)
+            s = srmr_score(a, sample_rate)
+        s[~np.isfinite(x).all(1)] = np.nan
+        score, A = torch.from_numpy(s), torch.from_numpy(a)
+    return (score, A) if return_energies else score
+
+
 # ----------------------------------------------------------------------------- DNSMOS
 # The reference's DNSMOS network (DNSMOS.py) in float32 torch ops from the checkpoint's tensors
 # (a dict of state-dict names -> float32 CPU tensors); engine: csrc/dnsmos.hip.

@@ -89,6 +89,8 @@ SIGNATURES = {
     "fsem_spectral_order": (ctypes.c_int, [_c_i32]),
     "fsem_spectral_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _vp,
                                           _vp]),
+    "fsem_srmr_channels": (ctypes.c_int, [_c_i32]),
+    "fsem_srmr_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

@@ -63,8 +63,8 @@ extern "C" {
 #define FSEM_ERATE -5         /* unsupported sample-rate pair (see resampling)      */
 
 const char *fsem_strerror(int code);
-/* (fsem_spectral_* joined at ABI 11 without a bump: entries that take no workspace add to the set
- * and change no existing entry, workspace size or layout.) */
+/* (fsem_spectral_* and fsem_srmr_* joined at ABI 11 without a bump: entries that take no workspace
+ * add to the set and change no existing entry, workspace size or layout.) */
 int fsem_version(void);  /* 11: + fsem_sdr_*; 10: + fsem_pesq_wb_frames_f32; 9: + fsem_pesq_bad_intervals_*, fsem_pesq_pool_f32; 8: + fsem_time_align_p862_*; 7: + fsem_host_buffer_mapped; 6: + fsem_build_id; 5: + fsem_time_align_utt_*; 4: + fsem_pre_emphasize_f32; 3: time alignment, distances */
 /* Content hash (16 hex digits) of the sources, headers and compile flags this library was built
  * from (fast_speech_enhancement_metrics_amd/_build.py source_hash); the host layer refuses a
@@ -429,6 +429,68 @@ int fsem_spectral_order(int32_t sample_rate);  /* LPC order P: 10 at 8000, 16 at
 int fsem_spectral_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
                       const int32_t *lengths, int32_t sample_rate, float *frames, int64_t ldf, float *fwsegsnr,
                       float *cd, float *is_, void *stream);
+
+/* ---------------------------------------------------------------- SRMR
+ * The speech-to-reverberation modulation energy ratio of a row (Falk, Zheng & Chan 2010), a
+ * no-reference measure: SRMRpy's full path (fast=False, norm=False, 23 channels, low_freq=125,
+ * min_cf=4, max_cf=128) with one change, the envelope (below).  An extension: the reference has no
+ * such measure.  Rows are scored at sample_rate fs, 8000 or 16000 Hz; a row holds n samples x[0 .. n).
+ *
+ * Centre frequencies.  EarQ = 9.26449, minBW = 24.7, c = EarQ minBW.  For i = 1 ... 23:
+ *   cf_i = -c + exp(i (ln(125 + c) - ln(fs / 2 + c)) / 23) (fs / 2 + c)
+ * (descending, cf_23 = 125); ERB(f) = f / EarQ + minBW.
+ *
+ * Analytic gammatone.  p_i = exp((-2 pi 1.019 ERB(cf_i) + j 2 pi cf_i) / fs).  Channel i has the complex
+ * impulse response h_i[m] = m^3 p_i^m / g_i, m >= 0 (the impulse-invariant sampling of t^3 e^{st}):
+ *   G_p(z) = p z^-1 (1 + 4 p z^-1 + p^2 z^-2) / (1 - p z^-1)^4,
+ * run from a zero state as the three-tap numerator followed by four first-order recurrences;
+ * g_i = |G_p(z0) + G_conj(p)(z0)| / 2 at z0 = exp(j 2 pi cf_i / fs), the gain at cf_i of the real filter
+ * Re h.  y_i = h_i * x.
+ *
+ * Envelope.  e_i[t] = |y_i[t]|.  (SRMRpy takes |hilbert(.)| of Slaney's real four-biquad cascade, a
+ * whole-row DFT per channel; Im y_i is the quadrature gammatone, which approximates that Hilbert
+ * transform.  The effect on the score: INTEGRATION.md section 13.)
+ *
+ * Modulation filters.  mcf_k = 4 32^(k / 7), k = 0 ... 7; Q = 2; W0 = tan(pi mcf_k / fs), B0 = W0 / Q;
+ * b = [B0, 0, -B0], a = [1 + B0 + W0^2, 2 W0^2 - 2, 1 - B0 + W0^2]; m_ik = the filter (b / a[0], a / a[0])
+ * applied to e_i from a zero state.
+ *
+ * Frames.  wl = ceil(0.256 fs) (4096 / 2048), wi = ceil(0.064 fs) (1024 / 512),
+ * w[m] = 0.54 - 0.46 cos(2 pi m / wl); F = 1 + (n - wl) / wi when n >= wl, else 0.
+ *   E[i, k, f] = sum_m (w[m] m_ik[f wi + m])^2,   A[i, k] = mean_f E[i, k, f]
+ *             = (1 / F) sum_t m_ik[t]^2 V[t],  V[t] = sum_f w^2[t - f wi] over the row's own F frames.
+ *
+ * Score.  ac_i = sum_k A[i, k], total = sum_i ac_i.  Walking i = 23, 22, ... (upward in frequency) and
+ * adding 100 ac_i / total, i* is the first i at which the sum is > 90; BW = ERB(cf_i*).
+ * L_k = mcf_k - tan(pi mcf_k / fs) / Q fs / (2 pi); K* = 8 if BW > L_7, else 7 if BW > L_6, else 6 if
+ * BW > L_5, else 5 (SRMRpy leaves K* undefined below L_4; elsewhere the rule is SRMRpy's).
+ *   SRMR = sum_i sum_{k < 4} A[i, k] / sum_i sum_{4 <= k < K*} A[i, k].
+ *
+ * Row conventions.  A row with F = 0 (n = 0 included) or with a non-finite sample among its first n is
+ * NaN, other rows are unaffected (the score kernel scans the row's samples itself; the energies of a
+ * row without a frame are NaN, those of a row with a non-finite sample whatever the arithmetic
+ * gives); a digitally silent row is NaN by 0 / 0.  Samples past a row's length are never read into a
+ * result.
+ *
+ * Precision and order.  The gammatone is float32 complex (its constants p^k are formed in double and
+ * rounded once), the envelope float32; the modulation filters' coefficients, state, squares and sums
+ * are double.  The kernel walks a row in tiles of 4096 samples: a gammatone lane takes 16 samples, a
+ * modulation lane a (filter, 128-sample segment) pair, states are carried by scans whose order depends
+ * on the sample index alone; a lane adds its m^2 V[t] in sample order, the 32 lanes of a filter are
+ * added in a fixed butterfly.  Sums over k and i run upward.  No floating-point atomics.
+ *   deg      : [batch, length] float32 (row stride ld >= length); read 4 bytes at a time, at any alignment
+ *   lengths  : NULL or [batch] int32 per-row lengths (Conventions)
+ *   energies : [batch][23][8] float64, required: A[i, k] of row b at energies[(b * 23 + i - 1) * 8 + k]
+ *   srmr     : [batch] float32 output
+ * Null pointers, batch < 0, ld < length and rows past 2^29 samples give FSEM_EINVAL before any launch;
+ * sample_rate other than 8000 or 16000 gives FSEM_ERATE (fsem_srmr_channels: 0).  batch == 0 gives
+ * FSEM_OK with nothing launched; length == 0 gives FSEM_OK with every score NaN.  No hidden device
+ * allocation, no workspace.  A row's score and energies are bitwise the same whatever the batch size,
+ * the row's position, `length`, `ld` and the stream.
+ */
+int fsem_srmr_channels(int32_t sample_rate);  /* gammatone channels: 23 at 8000 or 16000, 0 otherwise (host query) */
+int fsem_srmr_f32(const float *deg, int64_t batch, int64_t length, int64_t ld, const int32_t *lengths,
+                  int32_t sample_rate, double *energies, float *srmr, void *stream);
 
 #ifdef __cplusplus
 }
