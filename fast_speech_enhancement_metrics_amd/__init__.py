@@ -11,6 +11,7 @@
     Composite(16000, use_gpu=True)(clean, denoised)        -> [{"CSIG", "CBAK", "COVL", "PESQ", "LLR", "WSS", "SegSNR"}, ...]  (extension)
     SpectralMeasures(16000, use_gpu=True)(clean, denoised) -> [{"fwSegSNR", "CD", "IS"}, ...]  (extension)
     SRMR(sample_rate=16000, use_gpu=True)(None, denoised)   -> [{"SRMR": ...}, ...]  (extension, no reference signal)
+    BSSEval(16000, use_gpu=True)(sources, estimates)       -> [{"SDR", "SIR", "SAR"}, ...]  (extension; [B, S, L] mixtures)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
 """
@@ -23,9 +24,10 @@ from .Composite import Composite
 from .Spectral import SpectralMeasures
 from .LSD import LSD
 from .BSSSDR import BSSSDR
+from .BSSEval import BSSEval
 from .DNSMOS import DNSMOS
 from .SRMR import SRMR
 from .alignment import time_align
 
-__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "SpectralMeasures", "LSD", "BSSSDR", "DNSMOS", "SRMR",
-           "time_align"]
+__all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "SpectralMeasures", "LSD", "BSSSDR", "BSSEval",
+           "DNSMOS", "SRMR", "time_align"]

@@ -775,6 +775,108 @@ def bsssdr(clean: torch.Tensor, noisy: torch.Tensor, load_diag=None, filter_leng
     return torch.where(bad | ~torch.isfinite(coh), nan, val)
 
 
+# ----------------------------------------------------------------------------- BSS-eval of mixtures
+# SDR, SIR and SAR of E estimates against S sources (include/fsem.h "BSS-eval"; engine:
+# csrc/bsseval.hip): float32 normalisation, then float64 FFT correlations, the dense Gram matrix
+# of the sources' 512 delays and a Cholesky factorisation per mixture.
+BSSEVAL_MAX_SOURCES = 4
+BSSEVAL_CRITERIA = {None: 0, "SIR": 1, "SDR": 2}
+
+
+def _bsseval_mixture(s: torch.Tensor, h: torch.Tensor, K: int = 512):
+    """(coh [S, E], coh_all [E]) float64 of one unpadded mixture ([S, n] sources, [E, n] estimates);
+    all NaN by the NaN rule."""
+    S, n = s.shape
+    E = h.shape[0]
+    nan = float("nan")
+    bad = (torch.full((S, E), nan, dtype=torch.float64), torch.full((E,), nan, dtype=torch.float64))
+    s32, h32 = s.to(torch.float32), h.to(torch.float32)
+    if n + K - 1 < S * K or not (bool(torch.isfinite(s32).all()) and bool(torch.isfinite(h32).all())):
+        return bad
+
+    def unit(x):  # the norm in double, rounded to float32; the clamp and the quotient in float32
+        nrm = x.double().square().sum(1).sqrt().float().clamp(min=1e-6)
+        return (x / nrm[:, None]).double()
+
+    nfft = 1 << (n + K - 1).bit_length()  # >= n + K: no wrap-around within K lags
+    Sf = torch.fft.rfft(unit(s32), n=nfft)
+    Hf = torch.fft.rfft(unit(h32), n=nfft)
+    C = torch.fft.irfft(Sf.conj()[:, None] * Sf[None], n=nfft)[..., :K]  # C[i, j, k]
+    b = torch.fft.irfft(Sf.conj()[:, None] * Hf[None], n=nfft)[..., :K]  # b[i, e, k]
+    if not all(bool(C[i, i, 0] > 0) for i in range(S)):
+        return bad
+    full = torch.cat([C.transpose(0, 1).flip(2)[..., :-1], C], 2)  # lags -(K - 1) ... K - 1: C_ij[-k] = C_ji[k]
+    lag = torch.arange(K)[:, None] - torch.arange(K)[None, :] + K - 1
+    G = full[:, :, lag].permute(0, 2, 1, 3).reshape(S * K, S * K)  # G[(i, k), (j, l)] = C_ij[k - l]
+    d = b.permute(0, 2, 1).reshape(S * K, E)
+
+    def energy(M, rhs):
+        L, info = torch.linalg.cholesky_ex(M)
+        if int(info) != 0:
+            return None
+        y = torch.linalg.solve_triangular(L, rhs, upper=False)
+        return (y * y).sum(0)
+
+    coh = [energy(G[i * K:(i + 1) * K, i * K:(i + 1) * K], d[i * K:(i + 1) * K]) for i in range(S)]
+    if any(c is None for c in coh):
+        return bad
+    coh = torch.stack(coh)
+    coh_all = energy(G, d) if S > 1 else coh[0].clone()
+    if coh_all is None or not bool(torch.isfinite(coh).all() and torch.isfinite(coh_all).all()):
+        return bad
+    return coh, coh_all
+
+
+def bsseval(sources: torch.Tensor, estimates: torch.Tensor, lengths=None):
+    """[B, S, n] sources, [B, E, n] estimates (16 kHz) -> (coh [B, S, E], coh_all [B, E]) float64, the
+    energies of the estimates' projections on each source's and on all sources' 512 delays; mixtures
+    run on the host's threads.  ``lengths``: [B] ints, mixture b holds lengths[b] samples."""
+    B, S, n = sources.shape
+    E = estimates.shape[1]
+    lens = [n] * B if lengths is None else [int(v) for v in lengths]
+    outs = _host_map(lambda m: _bsseval_mixture(sources[m, :, :lens[m]], estimates[m, :, :lens[m]]), range(B))
+    if not B:
+        return torch.zeros(0, S, E, dtype=torch.float64), torch.zeros(0, E, dtype=torch.float64)
+    return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
+
+
+def bsseval_scores(coh: torch.Tensor, coh_all: torch.Tensor, criterion=None):
+    """(sdr, sir, sar [B, E] float32, perm [B, E] int32, sdr_mat, sir_mat [B, S, E] float32) from the
+    energies: the clamped ratios in dB and, with criterion "SIR" or "SDR" and E == S, the assignment
+    with the largest mean (the first of equal ones in itertools.permutations order)."""
+    import itertools
+    if criterion not in BSSEVAL_CRITERIA:
+        raise ValueError(f"permutation must be one of {list(BSSEVAL_CRITERIA)}, not {criterion!r}")
+    B, S, E = coh.shape
+
+    def db(num, den):
+        return 10.0 * torch.log10((num / den.clamp(min=1e-8)).clamp(min=1e-8))
+
+    ca = coh_all[:, None, :]
+    sd, si, sa = db(coh, 1.0 - coh), db(coh, ca - coh), db(coh_all, 1.0 - coh_all)
+    bad = torch.isnan(coh).flatten(1).any(1) | torch.isnan(coh_all).any(1)
+    perm = torch.arange(E, dtype=torch.int32).repeat(B, 1)
+    if criterion is not None and S == E:
+        crit = (si if criterion == "SIR" else sd).tolist()
+        for m in range(B):
+            if bool(bad[m]):
+                continue
+            best = None
+            for p in itertools.permutations(range(S)):
+                v = sum(crit[m][p[e]][e] for e in range(S)) / S
+                if best is None or v > best:
+                    best, arg = v, p
+            perm[m] = torch.tensor(arg, dtype=torch.int32)
+    idx = perm.long()[:, None, :]
+    nan = torch.full((), float("nan"), dtype=torch.float64)
+    sdr = torch.where(bad[:, None], nan, sd.gather(1, idx)[:, 0])
+    sir = torch.where(bad[:, None], nan, si.gather(1, idx)[:, 0])
+    sar = torch.where(bad[:, None], nan, sa)
+    sd = torch.where(bad[:, None, None], nan, sd)
+    si = torch.where(bad[:, None, None], nan, si)
+    return (sdr.float(), sir.float(), sar.float(), perm, sd.float(), si.float())
+
+
 # ----------------------------------------------------------------------------- Composite family
 # CSIG, CBAK, COVL with LLR and WSS (Hu & Loizou 2008; not in the reference; engine:
 # csrc/composite.hip, definitions: include/fsem_composite.h), float64, all frames of a chunk of

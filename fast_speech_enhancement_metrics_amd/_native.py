@@ -91,6 +91,12 @@ SIGNATURES = {
                                           _vp]),
     "fsem_srmr_channels": (ctypes.c_int, [_c_i32]),
     "fsem_srmr_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp]),
+    "fsem_bsseval_max_sources": (ctypes.c_int, []),
+    "fsem_bsseval_corr_doubles": (_c_i64, [_c_i32, _c_i32, _c_i64]),
+    "fsem_bsseval_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i32, _c_i32, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp,
+                                         _vp]),
+    "fsem_bsseval_scores_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

@@ -63,7 +63,7 @@ extern "C" {
 #define FSEM_ERATE -5         /* unsupported sample-rate pair (see resampling)      */
 
 const char *fsem_strerror(int code);
-/* (fsem_spectral_* and fsem_srmr_* joined at ABI 11 without a bump: entries that take no workspace
+/* (fsem_spectral_*, fsem_srmr_* and fsem_bsseval_* joined at ABI 11 without a bump: entries that take no workspace
  * add to the set and change no existing entry, workspace size or layout.) */
 int fsem_version(void);  /* 11: + fsem_sdr_*; 10: + fsem_pesq_wb_frames_f32; 9: + fsem_pesq_bad_intervals_*, fsem_pesq_pool_f32; 8: + fsem_time_align_p862_*; 7: + fsem_host_buffer_mapped; 6: + fsem_build_id; 5: + fsem_time_align_utt_*; 4: + fsem_pre_emphasize_f32; 3: time alignment, distances */
 /* Content hash (16 hex digits) of the sources, headers and compile flags this library was built
@@ -491,6 +491,74 @@ int fsem_spectral_f32(const float *ref, const float *deg, int64_t batch, int64_t
 int fsem_srmr_channels(int32_t sample_rate);  /* gammatone channels: 23 at 8000 or 16000, 0 otherwise (host query) */
 int fsem_srmr_f32(const float *deg, int64_t batch, int64_t length, int64_t ld, const int32_t *lengths,
                   int32_t sample_rate, double *energies, float *srmr, void *stream);
+
+/* ---------------------------------------------------------------- BSS-eval (SDR, SIR, SAR of mixtures)
+ * The energy ratios of mir_eval.separation.bss_eval_sources with a 512-tap distortion filter, for
+ * mixtures of several sources; fsem_bsssdr_f32 (fsem_bsssdr.h) is its one-source SDR.  An extension:
+ * the reference has no such metric.  Rows are scored as 16 kHz rows; 0-based indices.
+ *
+ * A mixture b has S sources s_i (i < S <= 4), E estimates h_e (e < E <= 4) and n = lengths[b] samples.
+ *  - Normalisation, every row, exactly as fsem_bsssdr.h states it: x' = x / max(|x|, 1e-6), the norm in
+ *    double rounded to float32, a float32 quotient.  Everything below is double.
+ *  - Correlations, k = 0 ... 511, samples outside [0, n) zero:
+ *      C_ij[k] = sum_t s'_i[t] s'_j[t + k] for all S^2 ordered pairs (C_ij[-k] = C_ji[k]),
+ *      b_ie[k] = sum_t s'_i[t] h'_e[t + k].
+ *  - Projections: coh[i, e] = b_ie^T T_i^-1 b_ie with T_i = Toeplitz(C_ii) (fsem_bsssdr_f32's coh of the
+ *    pair (i, e)); coh_all[e] = d^T G^-1 d with the S 512 x S 512 Gram matrix
+ *    G[(i, k), (j, l)] = C_ij[k - l] and d[(i, k)] = b_ie[k]: the energy of the projection of h'_e on
+ *    the 512 delays of all sources.  For S == 1, coh_all[e] is coh[0, e] itself.
+ *  - Scores, every denominator and every ratio clamped below at 1e-8 (all values within [-80, 80] dB):
+ *      SDR[i, e] = 10 log10(coh / (1 - coh)),  SIR[i, e] = 10 log10(coh / (coh_all[e] - coh)),
+ *      SAR[e] = 10 log10(coh_all / (1 - coh_all)).
+ *    These are bss_eval_sources' energies of s_target, e_interf and e_artif for the unit-norm estimate:
+ *    |e_interf|^2 = coh_all - coh (one source's span lies inside the span of all), |e_artif|^2 =
+ *    1 - coh_all.  A silent estimate gives -80 / -80 / -80; an estimate without interference (S == 1
+ *    included) has SIR = 80 + 10 log10(coh).
+ *  - NaN rule.  All outputs of a mixture are NaN (perm: the identity), and only that mixture's, when
+ *    any of its samples is non-finite, a source is silent (C_ii[0] == 0), n + 511 < S 512 (the delayed
+ *    sources cannot be independent; checked from n), or a recursion breaks down (a prediction-error
+ *    matrix that is not positive definite).  Exactly collinear sources are outside the definition:
+ *    whether rounding lets the recursion run through is not specified.
+ *  - Assignment.  With criterion 1 (SIR, as mir_eval) or 2 (SDR) and E == S, over the S! assignments
+ *    p (estimate e <-> source p[e]) in itertools.permutations order, the one with the largest mean over
+ *    e of the criterion's matrix entry [p[e], e] (summed over ascending e, divided by S, in double);
+ *    equal means keep the earlier assignment.  Otherwise p[e] = e.  Per estimate: SDR[p[e], e],
+ *    SIR[p[e], e], SAR[e], perm[e] = p[e].
+ *
+ * Two entries: fsem_bsseval_f32 forms the projections' energies, fsem_bsseval_scores_f32 turns them
+ * into scores (so SDRi needs no second scoring of the sources, and a test can hand it energies).
+ *   src, est : [batch, n_src, length] and [batch, n_est, length] float32; source row (b, i) starts at
+ *              src + (b n_src + i) ld, the estimates likewise; read 4 bytes at a time, at any alignment
+ *   lengths  : NULL or [batch] int32, one length per MIXTURE (Conventions)
+ *   norms    : [batch, n_src + n_est] float32 output, the rows' norms, sources first
+ *   corr     : [batch, fsem_bsseval_corr_doubles(n_src, n_est, length)] float64, the entry's only
+ *              scratch.  On return a mixture's block begins with the summed C_ij (all ordered pairs,
+ *              i-major: C_ij at (i n_src + j) 512) and then b_ie (at (n_src^2 + i n_est + e) 512), 512
+ *              doubles each; the per-chunk partial records and the norms' records follow.
+ *   coh      : [batch, n_src, n_est] float64;  coh_all : [batch, n_est] float64
+ *   criterion: 0 none, 1 SIR, 2 SDR
+ *   sdr, sir, sar : [batch, n_est] float32;  perm : [batch, n_est] int32
+ *   sdr_mat, sir_mat : NULL or [batch, n_src, n_est] float32
+ * Order of the sums (each depends on n alone): the sums of squares per chunk of 8192 samples, the
+ * correlations per chunk of 32768 samples exactly as fsem_bsssdr_f32 orders them (four consecutive
+ * quarters of each 2048-sample piece, added as ((q0 + q1) + q2) + q3), chunks in ascending order; the
+ * recursions are (block) Levinson recursions of one wave, their inner products added over the lanes'
+ * blocks l, l + 64, ... in ascending order and then by one xor butterfly.  No atomics, no hidden
+ * allocation.  A mixture's outputs are bitwise the same whatever the batch size, the mixture's
+ * position, `length`, `ld` and the stream.
+ * FSEM_EINVAL before any launch for null pointers (sdr_mat, sir_mat and lengths may be NULL), batch < 0,
+ * n_src or n_est outside 1 ... 4, length < 1, ld < length, length > 2^29, a criterion outside 0 ... 2,
+ * and, for the scores, n_est > n_src (p[e] = e names no source).  batch == 0 is FSEM_OK with nothing
+ * launched.
+ */
+int fsem_bsseval_max_sources(void);  /* 4 (host query) */
+int64_t fsem_bsseval_corr_doubles(int32_t n_src, int32_t n_est, int64_t length);  /* per mixture; 0 for refused arguments */
+int fsem_bsseval_f32(const float *src, const float *est, int64_t batch, int32_t n_src, int32_t n_est, int64_t length,
+                     int64_t ld, const int32_t *lengths, float *norms, double *corr, double *coh, double *coh_all,
+                     void *stream);
+int fsem_bsseval_scores_f32(const double *coh, const double *coh_all, int64_t batch, int32_t n_src, int32_t n_est,
+                            int32_t criterion, float *sdr, float *sir, float *sar, int32_t *perm, float *sdr_mat,
+                            float *sir_mat, void *stream);
 
 #ifdef __cplusplus
 }
