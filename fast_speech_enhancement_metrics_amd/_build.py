@@ -36,8 +36,8 @@ _ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # Joint front end 4.478 -> 4.392 ms per 4096-row launch, profiles/r5_pk/.  The back end
 # (pesq_back.hip) keeps it: its 49-band loops pack into fewer instructions with it.
 SOURCE_FLAGS = {"pesq.hip": ["-fno-slp-vectorize"], "stoi.hip": _ILP, "resample.hip": _ILP}
-HEADERS = ["fsem_common.h", "fsem_fft.h", "fsem_internal.h", "fsem_pesq.h", "fsem_resample.h", "fsem_tables.inc",
-           "fsem_vad.h"]
+HEADERS = ["fsem_build_marker.h", "fsem_common.h", "fsem_corr512.h", "fsem_fft.h", "fsem_internal.h", "fsem_lpc.h",
+           "fsem_pesq.h", "fsem_resample.h", "fsem_select.h", "fsem_speech_frames.h", "fsem_tables.inc", "fsem_vad.h"]
 HEADER_ABI = os.path.join(PKG, "..", "include", "fsem.h")
 COMPOSITE_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_composite.h")
 LSD_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_lsd.h")

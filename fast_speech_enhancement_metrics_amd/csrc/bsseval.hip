@@ -1,6 +1,8 @@
 // BSS-eval of mixtures: SDR, SIR and SAR of E estimates against S sources with a 512-tap
 // distortion filter (include/fsem.h, "BSS-eval"), an extension beside the one-source BSSSDR
-// (bsssdr.hip, whose norm and correlation schemes these kernels generalise).
+// (bsssdr.hip).  The two share the 512-lag direct correlation of fsem_corr512.h: its constants,
+// the LDS group layout, a wave's step loop and the four-wave reduction; each fills its own LDS
+// pieces, and the norm kernels and the solvers are each file's own.
 //
 //   bse_norm_partial  grid (norm chunk, signal).  As sdr_norm_partial, one sum of squares per
 //                     (signal, chunk of NC = 8192 samples); launched for the sources and for the
@@ -40,29 +42,18 @@
 // on the batch size, its position, the row capacity or the stream.
 #include <math.h>
 
-#include "fsem_common.h"
+#include "fsem_corr512.h"
 
 namespace fsem {
 namespace bsseval {
 
-constexpr int T = 256;
-constexpr int NWAVE = T / 64;
-constexpr int K = 512;          // filter length: lags 0 ... 511
-constexpr int NC = 8192;        // samples per record of a sum of squares
-constexpr int C = 32768;        // samples per record of partial correlations
-constexpr int SC = 2048;        // samples per piece in LDS
-constexpr int QT = SC / NWAVE;  // a wave's samples of a piece
-constexpr int G = 8;            // a group: 8 doubles, stored GP doubles apart
-constexpr int GP = 10;
+using namespace corr512;           // T, NWAVE, K, NC, C, SC, QT, G, GP, chunks, norm_chunks
 constexpr int NGA = SC / G;        // groups of the broadcast signal's piece
 constexpr int NGW = (SC + K) / G;  // groups of a window signal's extent
 constexpr int MAXS = 4;            // sources, and estimates, of a mixture
-static_assert(QT == K && K == 8 * 64, "a lane owns 8 lags; a wave's quarter of a piece is 512 samples");
-static_assert(C % SC == 0 && SC % T == 0 && K % T == 0, "pieces tile a chunk; the fill loop is block-uniform");
+static_assert(SC % T == 0 && K % T == 0, "the fill loop is block-uniform");
 static_assert(NGA * GP + 2 * NGW * GP >= NWAVE * 2 * K, "the four waves' sums fit the pieces' LDS");
 
-inline int64_t chunks(int64_t length) { return (length + C - 1) / C; }
-inline int64_t norm_chunks(int64_t length) { return (length + NC - 1) / NC; }
 __host__ __device__ inline int pairs(int S, int E) { return S * S + S * E; }  // correlations of a mixture
 // A mixture's block of `corr`: the summed correlations, the chunk records, the norm records.
 inline int64_t corr_doubles(int S, int E, int64_t length) {
@@ -114,18 +105,6 @@ __global__ __launch_bounds__(64) void bse_norms(const double *__restrict__ corr,
   norms[row] = nm < 1e-6f ? 1e-6f : nm;
 }
 
-// Element i of a piece's extent lies at gpad(i) doubles.
-__device__ __forceinline__ int gpad(int i) { return (i >> 3) * GP + (i & 7); }
-
-__device__ __forceinline__ void load_group(const double *g, double v[G]) {
-#pragma unroll
-  for (int e = 0; e < G; e += 2) {
-    const double2 d = *reinterpret_cast<const double2 *>(g + e);
-    v[e] = d.x;
-    v[e + 1] = d.y;
-  }
-}
-
 // Record of correlation (source i, window signal w) within a set of pairs(S, E) records: C_ij
 // (i-major) first, then b_ie.
 __device__ __forceinline__ int pair_index(int i, int w, int S, int E) {
@@ -170,47 +149,15 @@ __global__ __launch_bounds__(T) void bse_corr(const float *__restrict__ src, con
       W1[gpad(x)] = (double)(in && two ? row1[t] / n1 : 0.f);
     }
     __syncthreads();
-    const int g0 = wave * (QT / G);
-    double lo0[G], lo1[G];
-    load_group(W0 + (g0 + lane) * GP, lo0);
-    load_group(W1 + (g0 + lane) * GP, lo1);
-#pragma unroll 2  // (two steps swap the roles of the window's halves)
-    for (int st = 0; st < QT / G; ++st) {
-      if (p0 + G * (g0 + st) >= n) break;  // (wave-uniform: every s'_i[t] of the step is zero)
-      double a[G], hi0[G], hi1[G];
-      load_group(A + (g0 + st) * GP, a);                // group < NGA
-      load_group(W0 + (g0 + st + lane + 1) * GP, hi0);  // group <= 192 + 63 + 63 + 1 < NGW
-      load_group(W1 + (g0 + st + lane + 1) * GP, hi1);
-#pragma unroll
-      for (int u = 0; u < G; ++u) {
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-          const int w = u + j;  // lag 8 lane + j at sample t + u: element t + u + 8 lane + j
-          acc0[j] = fma(a[u], w < G ? lo0[w] : hi0[w - G], acc0[j]);
-          acc1[j] = fma(a[u], w < G ? lo1[w] : hi1[w - G], acc1[j]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < G; ++j) {
-        lo0[j] = hi0[j];
-        lo1[j] = hi1[j];
-      }
-    }
+    corr_quarter(A, W0, W1, wave, lane, p0, n, acc0, acc1);
   }
-  __syncthreads();
-  double *__restrict__ red = lds;  // [NWAVE][2 K]
-#pragma unroll
-  for (int j = 0; j < G; ++j) {
-    red[wave * 2 * K + G * lane + j] = acc0[j];
-    red[wave * 2 * K + K + G * lane + j] = acc1[j];
-  }
-  __syncthreads();
+  corr_gather(lds, wave, lane, acc0, acc1);
   double *__restrict__ rec = corr + b * stride + (int64_t)pairs(S, E) * K * (1 + c);
   double *__restrict__ out0 = rec + pair_index(i, w0, S, E) * K;
   double *__restrict__ out1 = rec + pair_index(i, two ? w1 : w0, S, E) * K;
 #pragma unroll
   for (int o = tid; o < 2 * K; o += T) {
-    const double v = ((red[o] + red[2 * K + o]) + red[4 * K + o]) + red[6 * K + o];
+    const double v = corr_total(lds, o);
     if (o < K) out0[o] = v;
     else if (two) out1[o - K] = v;
   }

@@ -7,7 +7,8 @@
 //                     in a fixed tree.  One 16-byte record per (row, chunk); no atomics.
 //   sdr_norms         one thread per row: the records in ascending order, the two norms
 //                     max((float)sqrt(sum), 1e-6f); NaN / inf for a row with a non-finite sample.
-//   sdr_corr          grid (chunk, row), 4 waves: the direct form of r[k] = sum_t s'[t] s'[t + k] and
+//   sdr_corr          grid (chunk, row), 4 waves (the step loop and the reduction are fsem_corr512.h's,
+//                     shared with bsseval.hip): the direct form of r[k] = sum_t s'[t] s'[t + k] and
 //                     b[k] = sum_t s'[t] h'[t + k], k = 0 ... 511, in double on the vector FMA
 //                     pipe, exact up to the rounding of the double sums.  A chunk is C = 32768 samples,
 //                     taken in pieces of SC = 2048: the block puts s'[t], h'[t] for
@@ -33,32 +34,20 @@
 #include <math.h>
 
 #include "../../include/fsem_bsssdr.h"
-#include "fsem_common.h"
+#include "fsem_build_marker.h"
+#include "fsem_corr512.h"
 
 namespace fsem {
 namespace bsssdr {
 
-constexpr int T = 256;          // threads of a block (4 waves)
-constexpr int NWAVE = T / 64;
-constexpr int K = 512;          // filter length: lags 0 ... 511
-constexpr int NC = 8192;        // samples per record of the sums of squares
-constexpr int C = 32768;        // samples per record of partial correlations
-constexpr int SC = 2048;        // samples per piece in LDS
-constexpr int QT = SC / NWAVE;  // a wave's samples of a piece
-constexpr int G = 8;            // a group: 8 doubles, stored GP doubles apart
-constexpr int GP = 10;
+using namespace corr512;          // T, NWAVE, K, NC, C, SC, QT, G, GP, chunks, norm_chunks
 constexpr int NG = (SC + K) / G;  // groups of a piece's extent
-static_assert(QT == K && K == 8 * 64, "a lane owns 8 lags; a wave's quarter of a piece is 512 samples");
-static_assert(C % SC == 0 && SC % (G * NWAVE) == 0, "pieces tile a chunk, steps tile a quarter");
 static_assert(2 * NG * GP >= NWAVE * 2 * K, "the four waves' sums fit the piece's LDS");
 
 struct Part {
   double ss, hh;  // sum s s, sum h h over the chunk's samples
 };
 static_assert(sizeof(Part) == 16, "one record is 16 bytes");
-
-inline int64_t chunks(int64_t length) { return (length + C - 1) / C; }
-inline int64_t norm_chunks(int64_t length) { return (length + NC - 1) / NC; }
 
 __global__ __launch_bounds__(T) void sdr_norm_partial(const float *__restrict__ ref, const float *__restrict__ deg,
                                                       int64_t ld, const int32_t *__restrict__ lengths, int length,
@@ -116,18 +105,6 @@ __global__ __launch_bounds__(64) void sdr_norms(const Part *__restrict__ part, i
   nrm[b] = make_float2(ns, nh);
 }
 
-// Element i of a piece's extent lies at gpad(i) doubles.
-__device__ __forceinline__ int gpad(int i) { return (i >> 3) * GP + (i & 7); }
-
-__device__ __forceinline__ void load_group(const double *g, double v[G]) {
-#pragma unroll
-  for (int e = 0; e < G; e += 2) {
-    const double2 d = *reinterpret_cast<const double2 *>(g + e);
-    v[e] = d.x;
-    v[e + 1] = d.y;
-  }
-}
-
 __global__ __launch_bounds__(T) void sdr_corr(const float *__restrict__ ref, const float *__restrict__ deg, int64_t ld,
                                               const int32_t *__restrict__ lengths, int length, int64_t r0,
                                               const float2 *__restrict__ nrm, double *__restrict__ part, int nchunk) {
@@ -158,45 +135,12 @@ __global__ __launch_bounds__(T) void sdr_corr(const float *__restrict__ ref, con
       H[gpad(i)] = (double)hq;
     }
     __syncthreads();
-    const int g0 = wave * (QT / G);
-    double loS[G], loH[G];
-    load_group(S + (g0 + lane) * GP, loS);
-    load_group(H + (g0 + lane) * GP, loH);
-#pragma unroll 2  // (two steps swap the roles of the window's halves: 19 register moves per 256 FMAs, not 64)
-    for (int st = 0; st < QT / G; ++st) {
-      if (p0 + G * (g0 + st) >= n) break;  // (wave-uniform: every s'[t] of the step is zero)
-      double a[G], hiS[G], hiH[G];
-      load_group(S + (g0 + st) * GP, a);
-      load_group(S + (g0 + st + lane + 1) * GP, hiS);
-      load_group(H + (g0 + st + lane + 1) * GP, hiH);
-#pragma unroll
-      for (int i = 0; i < G; ++i) {
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-          const int w = i + j;  // lag 8 lane + j at sample t + i: element t + i + 8 lane + j
-          accR[j] = fma(a[i], w < G ? loS[w] : hiS[w - G], accR[j]);
-          accB[j] = fma(a[i], w < G ? loH[w] : hiH[w - G], accB[j]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < G; ++j) {
-        loS[j] = hiS[j];
-        loH[j] = hiH[j];
-      }
-    }
+    corr_quarter(S, S, H, wave, lane, p0, n, accR, accB);  // s' is the broadcast signal and the first window
   }
-  __syncthreads();
-  double *__restrict__ red = lds;  // [NWAVE][2 K]
-#pragma unroll
-  for (int j = 0; j < G; ++j) {
-    red[wave * 2 * K + G * lane + j] = accR[j];
-    red[wave * 2 * K + K + G * lane + j] = accB[j];
-  }
-  __syncthreads();
+  corr_gather(lds, wave, lane, accR, accB);
   double *__restrict__ out = part + (row * nchunk + c) * (2 * K);
 #pragma unroll
-  for (int o = tid; o < 2 * K; o += T)
-    out[o] = ((red[o] + red[2 * K + o]) + red[4 * K + o]) + red[6 * K + o];
+  for (int o = tid; o < 2 * K; o += T) out[o] = corr_total(lds, o);
 }
 
 __global__ __launch_bounds__(64) void sdr_solve(const double *__restrict__ part, int nchunk,
@@ -300,17 +244,6 @@ inline Ws layout(Arena &a, int64_t batch, int64_t length) {
 }  // namespace fsem
 
 using namespace fsem;
-
-// The build's content hash, read from the file by the host layer (_build.library_build_id), as
-// libfsem.so's in runtime.hip.
-#ifndef FSEM_BUILD_ID
-#define FSEM_BUILD_ID "unknown"
-#endif
-__attribute__((used)) static const char kBsssdrBuildIdMarker[] = "FSEM_BUILD_ID:" FSEM_BUILD_ID;
-#ifndef FSEM_BUILD_ARCH
-#define FSEM_BUILD_ARCH "unknown"
-#endif
-__attribute__((used)) static const char kBsssdrBuildArchMarker[] = "FSEM_BUILD_ARCH:" FSEM_BUILD_ARCH;
 
 extern "C" int64_t fsem_bsssdr_filter_length(void) { return bsssdr::K; }
 

@@ -40,7 +40,10 @@
 #include <math.h>
 
 #include "../../include/fsem_composite.h"
+#include "fsem_build_marker.h"
 #include "fsem_internal.h"
+#include "fsem_select.h"
+#include "fsem_speech_frames.h"
 
 namespace fsem {
 namespace composite {
@@ -54,24 +57,19 @@ constexpr int GO = 15;      // table bin q of band i is spectrum bin f0_i - GO +
 constexpr int RT = 256;     // threads of a row block
 constexpr int CT = 64;      // threads of a combine block
 
-struct Geo {
-  int sr, hop, win, P, H, S;
+struct Geo : FrameGeo {
+  int H, S;
   int64_t C;  // samples a chunk owns: KF hops (it stages S = (KF + 3) hop)
 };
 
 inline bool make_geo(int32_t sr, Geo *g) {
-  if (sr != 8000 && sr != 16000) return false;
-  g->sr = sr;
-  g->hop = sr * 30 / 4000;
-  g->win = 4 * g->hop;
-  g->P = sr == 8000 ? 10 : 16;
+  if (!make_frame_geo(sr, g)) return false;
   g->H = sr == 8000 ? 256 : 512;
   g->S = (KF + 3) * g->hop;
   g->C = (int64_t)KF * g->hop;
   return true;
 }
 
-inline int64_t frames_of(int64_t n, const Geo &g) { return n >= g.win ? (n - g.win) / g.hop + 1 : 0; }
 inline int64_t chunks(int64_t length, const Geo &g) { return (length + g.C - 1) / g.C; }
 
 // Centre frequencies and bandwidths (Hz) of the 25 critical bands.
@@ -118,34 +116,6 @@ __device__ __forceinline__ float frame_db(float S, float D) {
   return fminf(fmaxf(v, -10.f), 35.f);
 }
 
-// One DPP move of a double (two 32-bit moves).
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov_d(double v) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = dpp_mov<CTRL>((uint32_t)b), hi = dpp_mov<CTRL>((uint32_t)(b >> 32));
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-
-// The wave's sums of N values at once, the same bits in every lane: pairwise exchanges only (a
-// lane and its partner add the same two numbers), inside a row of 16 lanes by DPP (quad
-// permutes, then the mirrors of 8 and 16 lanes), across rows by two xor exchanges; step by step
-// over all N so that the independent exchanges overlap.
-template <int N>
-__device__ __forceinline__ void wave_sums_d(double v[N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0xB1>(v[i]);  // quad_perm [1,0,3,2]
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x4E>(v[i]);  // quad_perm [2,3,0,1]
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x141>(v[i]);  // row_half_mirror
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x140>(v[i]);  // row_mirror
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], 16, 64);
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], 32, 64);
-}
-
 // R[k] = sum_t x[t] x[t + k], k = 0 .. P, over the windowed frame fw (win floats, then P zeros):
 // this lane's RUN samples against their successors (the lane's part: the caller sums over the wave).
 template <int P, int RUN>
@@ -165,7 +135,9 @@ __device__ __forceinline__ void autocorr(const float *__restrict__ fw, int lane,
 }
 
 // Prediction-error filter A = [1, a_1 .. a_P] of R by Levinson-Durbin, then q = A Toeplitz(Rs) A^T
-// = Rs[0] sum a_i^2 + 2 sum_k Rs[k] sum_i a_i a_{i+k}.
+// = Rs[0] sum a_i^2 + 2 sum_k Rs[k] sum_i a_i a_{i+k}: fsem_lpc.h's levinson and quadratic in one
+// body.  Written as those two calls it computes the same bits, but composite_frames then compiles
+// to other code (one index multiply signed, one or two more s_nop), so this one stays as it was.
 template <int P>
 __device__ __forceinline__ double lpc_quadratic(const double R[P + 1], const double Rs[P + 1]) {
   double a[P + 1];
@@ -247,7 +219,7 @@ __global__ __launch_bounds__(T) void composite_frames(const float *__restrict__ 
                                                       int64_t r0, Tables tb, FrameOut out, int64_t Fld,
                                                       int *__restrict__ flags, int nchunk) {
   constexpr int RUN = WIDE ? 8 : 4;
-  constexpr int hop = WIDE ? 120 : 60, win = 4 * hop, H = WIDE ? 512 : 256;
+  constexpr int hop = frame_hop(WIDE ? 16000 : 8000), win = 4 * hop, H = WIDE ? 512 : 256;
   constexpr int S = (KF + 3) * hop, FW = win + P;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2 *fbuf = reinterpret_cast<float2 *>(smem);       // [NWAVE][kFftBuf] (16-byte aligned rows)
@@ -279,7 +251,7 @@ __global__ __launch_bounds__(T) void composite_frames(const float *__restrict__ 
   if (tid < NB) gj0[tid] = tb.j0[tid];
   bad = __syncthreads_or(bad);
   if (tid == 0) flags[row * nchunk + c] = bad;
-  const int F = n >= win ? (n - win) / hop + 1 : 0;
+  const int F = frames_of(n, win, hop);
   float *fws = fw + wave * 2 * FW, *fwd = fws + FW;
   float2 *buf = fbuf + wave * kFftBuf;
   float *pw = reinterpret_cast<float *>(buf);  // [2][512] power spectra, after the transforms
@@ -347,25 +319,12 @@ __global__ __launch_bounds__(T) void composite_frames(const float *__restrict__ 
     for (int r = 0; r < (WIDE ? 8 : 4); ++r) {
       const int j = lane + 64 * r;
       if (WIDE) {
-        // X[j] = E + W^j O: E = (Z[j] + conj Z[512 - j]) / 2, O = (Z[j] - conj Z[512 - j]) / (2 i)
-        float amr = __shfl(va[7 - r].r, plane, 64), ami = __shfl(va[7 - r].i, plane, 64);
-        float bmr = __shfl(vb[7 - r].r, plane, 64), bmi = __shfl(vb[7 - r].i, plane, 64);
-        if (lane == 0) {
-          amr = va[(8 - r) & 7].r, ami = va[(8 - r) & 7].i;
-          bmr = vb[(8 - r) & 7].r, bmi = vb[(8 - r) & 7].i;
-        }
-        {
-          const float er = 0.5f * (va[r].r + amr), ei = 0.5f * (va[r].i - ami);
-          const float orr = 0.5f * (va[r].i + ami), oi = -0.5f * (va[r].r - amr);
-          const float xr = er + (wc[r] * orr + wsn[r] * oi), xi = ei + (wc[r] * oi - wsn[r] * orr);
-          pw[j] = xr * xr + xi * xi;
-        }
-        {
-          const float er = 0.5f * (vb[r].r + bmr), ei = 0.5f * (vb[r].i - bmi);
-          const float orr = 0.5f * (vb[r].i + bmi), oi = -0.5f * (vb[r].r - bmr);
-          const float xr = er + (wc[r] * orr + wsn[r] * oi), xi = ei + (wc[r] * oi - wsn[r] * orr);
-          pw[512 + j] = xr * xr + xi * xi;
-        }
+        cf am, bm;
+        split_mirrors(va, vb, r, lane, plane, am, bm);
+        const cf xa = split_bin(va[r], am, wc[r], wsn[r]);
+        pw[j] = xa.r * xa.r + xa.i * xa.i;
+        const cf xb = split_bin(vb[r], bm, wc[r], wsn[r]);
+        pw[512 + j] = xb.r * xb.r + xb.i * xb.i;
       } else {
         pw[j] = va[r].r * va[r].r + va[r].i * va[r].i;
         pw[512 + j] = vb[r].r * vb[r].r + vb[r].i * vb[r].i;
@@ -376,15 +335,7 @@ __global__ __launch_bounds__(T) void composite_frames(const float *__restrict__ 
     {
       const int sig = lane >> 5, i = lane & 31;
       if (i < NB) {
-        const int j0 = gj0[i];
-        const float *__restrict__ g = gt + i * GW;
-        const float *__restrict__ p = pw + sig * 512;
-        float acc = 0.f;
-#pragma unroll
-        for (int qq = 0; qq < GW; ++qq) {
-          const int j = j0 + qq;
-          if (j >= 0 && j < H) acc = fmaf(p[j], g[qq], acc);
-        }
+        const float acc = band_sum<GW>(pw + sig * 512, gt + i * GW, gj0[i], H);
         e[sig * 32 + i] = 10.f * log10f(fmaxf(acc, 1e-10f));
       }
     }
@@ -418,30 +369,21 @@ __global__ __launch_bounds__(T) void composite_frames(const float *__restrict__ 
   }
 }
 
-// The float's bits as an unsigned key in the floats' order, every NaN after +inf.
-__device__ __forceinline__ uint32_t order_key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  if (v != v) return 0xFFFFFFFFu;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);  // (0xFFFFFFFF: a NaN)
-}
-
 __global__ __launch_bounds__(RT) void composite_rows(FrameOut fr, int64_t Fld, int64_t B,
                                                      const int32_t *__restrict__ lengths, int length, int hop,
                                                      float *__restrict__ llr, float *__restrict__ wss,
                                                      float *__restrict__ seg) {
-  __shared__ int hist[256];
-  __shared__ uint32_t s_prefix;
-  __shared__ int s_need;
-  __shared__ double red[RT / 64];
+  static_assert(RT == 256, "select_kth is a 256-thread block's");
+  __shared__ struct {
+    SelectLds sel;
+    double red[RT / 64];
+  } s;
   const int which = blockIdx.x, tid = threadIdx.x;
   const int64_t row = grid_row_yz();
   if (row >= B) return;
   const int n = row_length(lengths, row, length);
   const int win = 4 * hop;
-  const int F = n >= win ? (n - win) / hop + 1 : 0;
+  const int F = frames_of(n, win, hop);
   float *__restrict__ dst = which == 0 ? llr : which == 1 ? wss : seg;
   if (F == 0) {
     if (tid == 0) dst[row] = __builtin_nanf("");
@@ -452,45 +394,17 @@ __global__ __launch_bounds__(RT) void composite_rows(FrameOut fr, int64_t Fld, i
   const int K = trimmed ? (int)((19 * (int64_t)F + 10) / 20) : F;
   uint32_t kth = 0xFFFFFFFFu;  // the K-th smallest key
   int need = 0;                // copies of it among the K smallest
-  if (trimmed) {
-    uint32_t prefix = 0;
-    need = K;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      const uint32_t mask = pass ? 0xFFFFFFFFu << (shift + 8) : 0u;
-      hist[tid] = 0;  // (RT == 256 bins)
-      __syncthreads();
-      for (int i = tid; i < F; i += RT) {
-        const uint32_t k = order_key(v[i]);
-        if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255], 1);  // integer counts: no order
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int cum = 0, b = 0;
-        for (; b < 255; ++b) {
-          if (cum + hist[b] >= need) break;
-          cum += hist[b];
-        }
-        s_prefix = prefix | ((uint32_t)b << shift);
-        s_need = need - cum;
-      }
-      __syncthreads();
-      prefix = s_prefix;
-      need = s_need;
-      __syncthreads();
-    }
-    kth = prefix;
-  }
+  if (trimmed) kth = select_kth(v, F, K, s.sel, &need);  // (block-uniform)
   double acc = 0.0;
   for (int i = tid; i < F; i += RT) {
     const float x = v[i];
     if (!trimmed || order_key(x) < kth) acc += (double)x;
   }
   acc = wave_sum_d(acc);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  if ((tid & 63) == 0) s.red[tid >> 6] = acc;
   __syncthreads();
   if (tid == 0) {
-    double total = (red[0] + red[1]) + (red[2] + red[3]);
+    double total = (s.red[0] + s.red[1]) + (s.red[2] + s.red[3]);
     if (trimmed) total += (double)need * (double)key_value(kth);
     dst[row] = (float)(total / (double)K);
   }
@@ -546,7 +460,7 @@ inline Ws layout(Arena &a, int64_t batch, int64_t length, const Geo &g) {
   w.tb.g = a.take<float>((size_t)NB * GW);
   w.tb.j0 = a.take<int>(32);
   w.tb.tw = a.take<float>(1024);
-  w.Fld = std::max<int64_t>(frames_of(length, g), 1);
+  w.Fld = std::max<int64_t>(frames_of(length, g.win, g.hop), 1);
   w.fr.llr = a.take<float>((size_t)batch * (size_t)w.Fld);
   w.fr.wss = a.take<float>((size_t)batch * (size_t)w.Fld);
   w.fr.seg = a.take<float>((size_t)batch * (size_t)w.Fld);
@@ -568,17 +482,6 @@ inline Ws layout(Arena &a, int64_t batch, int64_t length, const Geo &g) {
 }  // namespace fsem
 
 using namespace fsem;
-
-// The build's content hash, read from the file by the host layer (_build.library_build_id), as
-// libfsem.so's in runtime.hip.
-#ifndef FSEM_BUILD_ID
-#define FSEM_BUILD_ID "unknown"
-#endif
-__attribute__((used)) static const char kCompositeBuildIdMarker[] = "FSEM_BUILD_ID:" FSEM_BUILD_ID;
-#ifndef FSEM_BUILD_ARCH
-#define FSEM_BUILD_ARCH "unknown"
-#endif
-__attribute__((used)) static const char kCompositeBuildArchMarker[] = "FSEM_BUILD_ARCH:" FSEM_BUILD_ARCH;
 
 extern "C" int64_t fsem_composite_chunk(int32_t sample_rate) {
   composite::Geo g;

@@ -37,6 +37,7 @@
 #include <math.h>
 
 #include "../../include/fsem_dnsmos.h"
+#include "fsem_build_marker.h"
 #include "fsem_common.h"
 
 namespace fsem {
@@ -531,17 +532,6 @@ inline int run(const float *deg, int64_t batch, int64_t length, int64_t ld, cons
 }  // namespace fsem
 
 using namespace fsem;
-
-// The build's content hash, read from the file by the host layer (_build.library_build_id), as
-// libfsem.so's in runtime.hip.
-#ifndef FSEM_BUILD_ID
-#define FSEM_BUILD_ID "unknown"
-#endif
-__attribute__((used)) static const char kDnsmosBuildIdMarker[] = "FSEM_BUILD_ID:" FSEM_BUILD_ID;
-#ifndef FSEM_BUILD_ARCH
-#define FSEM_BUILD_ARCH "unknown"
-#endif
-__attribute__((used)) static const char kDnsmosBuildArchMarker[] = "FSEM_BUILD_ARCH:" FSEM_BUILD_ARCH;
 
 extern "C" int64_t fsem_dnsmos_segments(int64_t length) { return dnsmos::segs_of(length); }
 

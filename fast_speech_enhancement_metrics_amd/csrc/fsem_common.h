@@ -93,6 +93,34 @@ __device__ __forceinline__ T dpp_mov(T v) {
   return __builtin_bit_cast(T, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
 }
 
+// One DPP move of a double (two 32-bit moves).
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov_d(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = dpp_mov<CTRL>((uint32_t)b), hi = dpp_mov<CTRL>((uint32_t)(b >> 32));
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+// The wave's sums of N values at once, the same bits in every lane: pairwise exchanges only (a
+// lane and its partner add the same two numbers), inside a row of 16 lanes by DPP (quad
+// permutes, then the mirrors of 8 and 16 lanes), across rows by two xor exchanges; step by step
+// over all N so that the independent exchanges overlap.  (Another order than wave_sum_d's.)
+template <int N>
+__device__ __forceinline__ void wave_sums_d(double v[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0xB1>(v[i]);  // quad_perm [1,0,3,2]
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x4E>(v[i]);  // quad_perm [2,3,0,1]
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x141>(v[i]);  // row_half_mirror
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x140>(v[i]);  // row_mirror
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], 16, 64);
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], 32, 64);
+}
+
 // Row length of utterance b: the per-row length when given (clamped to [0, L]), else L; in L's
 // type (int64_t, or int where the kernel's row arithmetic is 32-bit).
 template <class Len>

@@ -35,6 +35,7 @@
 #include <math.h>
 
 #include "../../include/fsem_lsd.h"
+#include "fsem_build_marker.h"
 #include "fsem_common.h"
 
 namespace fsem {
@@ -347,17 +348,6 @@ inline Ws layout(Arena &a, int64_t batch, int64_t length) {
 }  // namespace fsem
 
 using namespace fsem;
-
-// The build's content hash, read from the file by the host layer (_build.library_build_id), as
-// libfsem.so's in runtime.hip.
-#ifndef FSEM_BUILD_ID
-#define FSEM_BUILD_ID "unknown"
-#endif
-__attribute__((used)) static const char kLsdBuildIdMarker[] = "FSEM_BUILD_ID:" FSEM_BUILD_ID;
-#ifndef FSEM_BUILD_ARCH
-#define FSEM_BUILD_ARCH "unknown"
-#endif
-__attribute__((used)) static const char kLsdBuildArchMarker[] = "FSEM_BUILD_ARCH:" FSEM_BUILD_ARCH;
 
 extern "C" int64_t fsem_lsd_frames(int64_t length) { return length < 0 ? 0 : lsd::frames_of(length); }
 

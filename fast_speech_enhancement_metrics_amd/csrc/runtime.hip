@@ -5,6 +5,7 @@
 #include <atomic>
 #include <mutex>
 
+#include "fsem_build_marker.h"
 #include "fsem_internal.h"
 
 using namespace fsem;
@@ -91,19 +92,8 @@ extern "C" const char *fsem_strerror(int code) {
 
 extern "C" int fsem_version(void) { return 11; }  // 11: + fsem_sdr_*; 10: + fsem_pesq_wb_frames_f32; 9: + fsem_pesq_bad_intervals_*, fsem_pesq_pool_f32; 8: + fsem_time_align_p862_*; 7: + fsem_host_buffer_mapped; 6: + fsem_build_id; 5: + fsem_time_align_utt_*; 4: + fsem_pre_emphasize_f32; 3: + fsem_time_align_*, fsem_pesq_distances_*
 
-// The build's content hash (_build.py passes -DFSEM_BUILD_ID); the marker prefix lets the host
-// layer read the id from the file without loading it (_build.library_build_id).
-#ifndef FSEM_BUILD_ID
-#define FSEM_BUILD_ID "unknown"
-#endif
-static const char kBuildIdMarker[] = "FSEM_BUILD_ID:" FSEM_BUILD_ID;
-extern "C" const char *fsem_build_id(void) { return kBuildIdMarker + 14; }
-// The offload target, recorded apart from the content hash (_build.library_build_arch): a library
-// built for another target is refused at load rather than rebuilt.
-#ifndef FSEM_BUILD_ARCH
-#define FSEM_BUILD_ARCH "unknown"
-#endif
-__attribute__((used)) static const char kBuildArchMarker[] = "FSEM_BUILD_ARCH:" FSEM_BUILD_ARCH;
+// The build's content hash, without the marker's prefix (fsem_build_marker.h).
+extern "C" const char *fsem_build_id(void) { return kBuildIdMarker + kBuildIdPrefix; }
 
 // The drop-in call's scores go straight into its pinned host buffer when the runtime maps that
 // buffer into the device address space at the same address (hipHostMalloc memory on ROCm).

@@ -1,7 +1,11 @@
 // Spectral measures of (clean, denoised) rows from Hu & Loizou's evaluation set: the
 // frequency-weighted segmental SNR (fwSegSNR), the LPC cepstral distance (CD) and the
 // Itakura-Saito distance (IS) (include/fsem.h "Spectral").  Replaces nothing in the reference.
-// Composite's frames, window, LPC orders and band filters; none of its code.
+// Composite's frames, window, LPC orders and band filters, through the code the two share: the
+// frame geometry, the spectra's split step and the band sums (fsem_speech_frames.h), the radix
+// select (fsem_select.h) and the wave's double sums (fsem_common.h); the LPC recursion and the
+// quadratic form are fsem_lpc.h's.  The tables here are constants (fsem_tables.inc), Composite's
+// its own.
 //
 //   spectral_frames  grid (group, row), 4 waves.  A group is KF = 32 frames: its (KF + 3) hop
 //                    samples of both rows are staged in LDS once (frames overlap by 75 %).
@@ -35,7 +39,9 @@
 #include <algorithm>
 #include <math.h>
 
-#include "fsem_fft.h"
+#include "fsem_lpc.h"
+#include "fsem_select.h"
+#include "fsem_speech_frames.h"
 
 namespace fsem {
 namespace spectral {
@@ -47,92 +53,12 @@ constexpr int NB = 25;  // critical bands
 constexpr int GW = FSEM_SPEC_GW;
 constexpr int RT = 256;  // threads of a row block
 
-struct Geo {
-  int sr, hop, win, P;
-};
-
-inline bool make_geo(int32_t sr, Geo *g) {
-  if (sr != 8000 && sr != 16000) return false;
-  g->sr = sr;
-  g->hop = sr * 30 / 4000;
-  g->win = 4 * g->hop;
-  g->P = sr == 8000 ? 10 : 16;
-  return true;
-}
-
-inline int64_t frames_of(int64_t n, const Geo &g) { return n >= g.win ? (n - g.win) / g.hop + 1 : 0; }
-
-// One DPP move of a double (two 32-bit moves).
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov_d(double v) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = dpp_mov<CTRL>((uint32_t)b), hi = dpp_mov<CTRL>((uint32_t)(b >> 32));
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-
-// The wave's sums of N values at once, the same bits in every lane: pairwise exchanges only (a
-// lane and its partner add the same two numbers), inside a row of 16 lanes by DPP, across rows by
-// two xor exchanges; step by step over all N so that the independent exchanges overlap.
-template <int N>
-__device__ __forceinline__ void wave_sums_d(double v[N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0xB1>(v[i]);  // quad_perm [1,0,3,2]
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x4E>(v[i]);  // quad_perm [2,3,0,1]
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x141>(v[i]);  // row_half_mirror
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += dpp_mov_d<0x140>(v[i]);  // row_mirror
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], 16, 64);
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], 32, 64);
-}
-
-// Prediction-error filter a = [1, a_1 .. a_P] of R by Levinson-Durbin (R[0] == 0: NaN by 0 / 0).
-template <int P>
-__device__ __forceinline__ void levinson(const double *__restrict__ R, double a[P + 1]) {
-  a[0] = 1.0;
-#pragma unroll
-  for (int i = 1; i <= P; ++i) a[i] = 0.0;
-  double E = R[0];
-#pragma unroll
-  for (int i = 1; i <= P; ++i) {
-    double acc = R[i];
-#pragma unroll
-    for (int j = 1; j < i; ++j) acc = fma(a[j], R[i - j], acc);
-    const double k = -acc / E;
-#pragma unroll
-    for (int j = 1; 2 * j <= i; ++j) {
-      const double u = a[j], v = a[i - j];
-      a[j] = fma(k, v, u);
-      if (j != i - j) a[i - j] = fma(k, u, v);
-    }
-    a[i] = k;
-    E *= 1.0 - k * k;
-  }
-}
-
-// a Toeplitz(R) a^T = R[0] sum a_i^2 + 2 sum_k R[k] sum_i a_i a_{i+k}.
-template <int P>
-__device__ __forceinline__ double quadratic(const double a[P + 1], const double *__restrict__ R) {
-  double q = 0.0;
-#pragma unroll
-  for (int k = P; k >= 0; --k) {
-    double c = 0.0;
-#pragma unroll
-    for (int i = 0; i + k <= P; ++i) c = fma(a[i], a[i + k], c);
-    q = fma(k ? 2.0 * c : c, R[k], q);
-  }
-  return q;
-}
-
 template <int P, bool WIDE>
 __global__ __launch_bounds__(T) void spectral_frames(const float *__restrict__ ref, const float *__restrict__ deg,
                                                      int64_t ld, const int32_t *__restrict__ lengths, int length,
                                                      int64_t r0, int64_t batch, float *__restrict__ frames,
                                                      int64_t ldf) {
-  constexpr int hop = WIDE ? 120 : 60, win = 4 * hop, H = WIDE ? 512 : 256;
+  constexpr int hop = frame_hop(WIDE ? 16000 : 8000), win = 4 * hop, H = WIDE ? 512 : 256;
   constexpr int S = (KF + 3) * hop;   // samples a group's frames cover
   constexpr int NK = (win + 63) / 64;  // window samples per lane
   constexpr int NR = WIDE ? 8 : 4;     // spectrum bins per lane
@@ -149,7 +75,7 @@ __global__ __launch_bounds__(T) void spectral_frames(const float *__restrict__ r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t row = r0 + blockIdx.y;
   const int n = row_length(lengths, row, length);
-  const int F = n >= win ? (n - win) / hop + 1 : 0;
+  const int F = frames_of(n, win, hop);
   const int f0 = blockIdx.x * KF;
   if (f0 >= F) return;  // (block-uniform, before any barrier)
   const float *__restrict__ srow = ref + row * ld;
@@ -251,25 +177,12 @@ __global__ __launch_bounds__(T) void spectral_frames(const float *__restrict__ r
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
       if (WIDE) {
-        // X[j] = E + W^j O: E = (Z[j] + conj Z[512 - j]) / 2, O = (Z[j] - conj Z[512 - j]) / (2 i)
-        float amr = __shfl(va[7 - r].r, plane, 64), ami = __shfl(va[7 - r].i, plane, 64);
-        float bmr = __shfl(vb[7 - r].r, plane, 64), bmi = __shfl(vb[7 - r].i, plane, 64);
-        if (lane == 0) {
-          amr = va[(8 - r) & 7].r, ami = va[(8 - r) & 7].i;
-          bmr = vb[(8 - r) & 7].r, bmi = vb[(8 - r) & 7].i;
-        }
-        {
-          const float er = 0.5f * (va[r].r + amr), ei = 0.5f * (va[r].i - ami);
-          const float orr = 0.5f * (va[r].i + ami), oi = -0.5f * (va[r].r - amr);
-          const float xr = er + (wc[r] * orr + wsn[r] * oi), xi = ei + (wc[r] * oi - wsn[r] * orr);
-          ma[r] = sqrtf(xr * xr + xi * xi);
-        }
-        {
-          const float er = 0.5f * (vb[r].r + bmr), ei = 0.5f * (vb[r].i - bmi);
-          const float orr = 0.5f * (vb[r].i + bmi), oi = -0.5f * (vb[r].r - bmr);
-          const float xr = er + (wc[r] * orr + wsn[r] * oi), xi = ei + (wc[r] * oi - wsn[r] * orr);
-          mb[r] = sqrtf(xr * xr + xi * xi);
-        }
+        cf am, bm;
+        split_mirrors(va, vb, r, lane, plane, am, bm);
+        const cf xa = split_bin(va[r], am, wc[r], wsn[r]);
+        ma[r] = sqrtf(xa.r * xa.r + xa.i * xa.i);
+        const cf xb = split_bin(vb[r], bm, wc[r], wsn[r]);
+        mb[r] = sqrtf(xb.r * xb.r + xb.i * xb.i);
       } else {
         ma[r] = sqrtf(va[r].r * va[r].r + va[r].i * va[r].i);
         mb[r] = sqrtf(vb[r].r * vb[r].r + vb[r].i * vb[r].i);
@@ -293,18 +206,7 @@ __global__ __launch_bounds__(T) void spectral_frames(const float *__restrict__ r
     // band sums: lanes 0 .. 24 the clean frame's, lanes 32 .. 56 the denoised frame's
     {
       const int sig = lane >> 5, i = lane & 31;
-      if (i < NB) {
-        const int j0 = gj0[i];
-        const float *__restrict__ g = gt + i * GW;
-        const float *__restrict__ p = pw + sig * 512;
-        float acc = 0.f;
-#pragma unroll
-        for (int qq = 0; qq < GW; ++qq) {
-          const int j = j0 + qq;
-          if (j >= 0 && j < H) acc = fmaf(p[j], g[qq], acc);
-        }
-        e[sig * 32 + i] = acc;
-      }
+      if (i < NB) e[sig * 32 + i] = band_sum<GW>(pw + sig * 512, gt + i * GW, gj0[i], H);
     }
     wave_lds_fence();
     double nd[2] = {0.0, 0.0};
@@ -360,20 +262,9 @@ __global__ __launch_bounds__(T) void spectral_frames(const float *__restrict__ r
   if (live) frames[((sig ? 2 : 1) * batch + row) * ldf + f] = sig ? (float)is : (float)cd;
 }
 
-// The float's bits as an unsigned key in the floats' order, every NaN after +inf.
-__device__ __forceinline__ uint32_t order_key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  if (v != v) return 0xFFFFFFFFu;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);  // (0xFFFFFFFF: a NaN)
-}
-
+static_assert(RT == 256, "select_kth is a 256-thread block's");
 struct RowLds {
-  int hist[256];
-  uint32_t prefix;
-  int need;
+  SelectLds sel;
   double red[RT];
 };
 
@@ -383,35 +274,7 @@ __device__ float row_mean(const float *__restrict__ v, int F, bool trimmed, RowL
   const int K = trimmed ? (int)((19 * (int64_t)F + 10) / 20) : F;
   uint32_t kth = 0xFFFFFFFFu;  // the K-th smallest key
   int need = 0;                // copies of it among the K smallest
-  if (trimmed) {
-    uint32_t prefix = 0;
-    need = K;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      const uint32_t mask = pass ? 0xFFFFFFFFu << (shift + 8) : 0u;
-      s.hist[tid] = 0;  // (RT == 256 bins)
-      __syncthreads();
-      for (int i = tid; i < F; i += RT) {
-        const uint32_t k = order_key(v[i]);
-        if ((k & mask) == prefix) atomicAdd(&s.hist[(k >> shift) & 255], 1);  // integer counts: no order
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int cum = 0, b = 0;
-        for (; b < 255; ++b) {
-          if (cum + s.hist[b] >= need) break;
-          cum += s.hist[b];
-        }
-        s.prefix = prefix | ((uint32_t)b << shift);
-        s.need = need - cum;
-      }
-      __syncthreads();
-      prefix = s.prefix;
-      need = s.need;
-      __syncthreads();
-    }
-    kth = prefix;
-  }
+  if (trimmed) kth = select_kth(v, F, K, s.sel, &need);
   double acc = 0.0;
   for (int i = tid; i < F; i += RT) {
     const float x = v[i];
@@ -440,7 +303,7 @@ __global__ __launch_bounds__(RT) void spectral_rows(const float *__restrict__ re
   if (row >= batch) return;
   const int n = row_length(lengths, row, length);
   const int win = 4 * hop;
-  const int F = n >= win ? (n - win) / hop + 1 : 0;
+  const int F = frames_of(n, win, hop);
   const float *__restrict__ srow = ref + row * ld;
   const float *__restrict__ hrow = deg + row * ld;
   int bad = 0;
@@ -467,8 +330,8 @@ __global__ __launch_bounds__(RT) void spectral_rows(const float *__restrict__ re
 using namespace fsem;
 
 extern "C" int fsem_spectral_order(int32_t sample_rate) {
-  spectral::Geo g;
-  return spectral::make_geo(sample_rate, &g) ? g.P : 0;
+  FrameGeo g;
+  return make_frame_geo(sample_rate, &g) ? g.P : 0;
 }
 
 extern "C" int fsem_spectral_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
@@ -477,9 +340,9 @@ extern "C" int fsem_spectral_f32(const float *ref, const float *deg, int64_t bat
   if (!ref || !deg || !frames || !fwsegsnr || !cd || !is_ || batch < 0 || length < 0 || ld < length ||
       length > kMaxLength)
     return FSEM_EINVAL;
-  spectral::Geo g;
-  if (!spectral::make_geo(sample_rate, &g)) return FSEM_ERATE;
-  const int64_t F = spectral::frames_of(length, g);
+  FrameGeo g;
+  if (!make_frame_geo(sample_rate, &g)) return FSEM_ERATE;
+  const int64_t F = frames_of(length, g.win, g.hop);
   if (ldf < std::max<int64_t>(F, 1)) return FSEM_EINVAL;
   if (batch == 0) return FSEM_OK;  // (nothing to score)
   hipStream_t st = (hipStream_t)stream;

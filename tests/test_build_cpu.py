@@ -13,7 +13,7 @@ from fast_speech_enhancement_metrics_amd import _build, _native
 def test_every_included_header_is_a_build_dependency():
     import re
     deps = {os.path.basename(d) for d in _build.deps()}
-    for src in _build.SOURCES + _build.HEADERS:
+    for src in [src for lib in _build.LIBRARIES for src in lib.sources] + _build.HEADERS:
         text = open(os.path.join(_build.CSRC, src)).read()
         for inc in re.findall(r'#include\s+"([^"]+)"', text):
             assert os.path.basename(inc) in deps, (src, inc)
