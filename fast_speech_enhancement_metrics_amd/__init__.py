@@ -12,6 +12,7 @@
     SpectralMeasures(16000, use_gpu=True)(clean, denoised) -> [{"fwSegSNR", "CD", "IS"}, ...]  (extension)
     SRMR(sample_rate=16000, use_gpu=True)(None, denoised)   -> [{"SRMR": ...}, ...]  (extension, no reference signal)
     BSSEval(16000, use_gpu=True)(sources, estimates)       -> [{"SDR", "SIR", "SAR"}, ...]  (extension; [B, S, L] mixtures)
+    PITSDR(16000, use_gpu=True)(sources, estimates)        -> [{"SI-SDR", "SNR"}, ...]  (extension; best assignment, .loss() is differentiable)
 
 Ragged batches: pass lists of 1-D utterances, or padded [B, L] tensors with ``lengths=``.
 """
@@ -25,9 +26,10 @@ from .Spectral import SpectralMeasures
 from .LSD import LSD
 from .BSSSDR import BSSSDR
 from .BSSEval import BSSEval
+from .PITSDR import PITSDR
 from .DNSMOS import DNSMOS
 from .SRMR import SRMR
 from .alignment import time_align
 
 __all__ = ["BaseMetric", "PESQ", "STOI", "PESQ_STOI", "SDR", "Composite", "SpectralMeasures", "LSD", "BSSSDR", "BSSEval",
-           "DNSMOS", "SRMR", "time_align"]
+           "PITSDR", "DNSMOS", "SRMR", "time_align"]

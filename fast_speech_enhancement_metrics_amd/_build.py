@@ -21,7 +21,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 STAMP_LIB = os.path.join(LIBDIR, "libfsem_stamps.so")  # diagnostic build (tools/stamps.py)
 SOURCES = ["pesq.hip", "pesq_back.hip", "stoi.hip", "resample.hip", "align.hip", "sdr.hip", "spectral.hip",
-           "srmr.hip", "bsseval.hip", "runtime.hip"]
+           "srmr.hip", "bsseval.hip", "pitsdr.hip", "runtime.hip"]
 # per-source code-generation flags: the STOI kernels and the resamplers are scheduled for ILP
 # (gfx950's max-ilp machine scheduler: joint call 7.167 vs 7.198 ms, profiles/r4_sc/; config 5
 # 224.0k vs 221.3k utt/s, profiles/r4_fl/; bitwise equal); the PESQ front end keeps the
@@ -57,8 +57,8 @@ class Library(NamedTuple):
 # every library of the package, in build order, all built from one content hash.  Each metric
 # after the core has a library of its own (the four metric libraries' entry sets are pinned name by
 # name, and so are the core's workspace queries and the entries that take a workspace: the core
-# still takes entries without one, as fsem_spectral_* in spectral.hip, fsem_srmr_* in srmr.hip and
-# fsem_bsseval_* in bsseval.hip); they
+# still takes entries without one, as fsem_spectral_* in spectral.hip, fsem_srmr_* in srmr.hip,
+# fsem_bsseval_* in bsseval.hip and fsem_pitsdr_* in pitsdr.hip); they
 # use fsem_common.h (the Arena, the launch helpers) and link alone, except Composite's, whose
 # PESQ stage calls into libfsem.so.  A further library is one more entry here, a binding table in
 # _native, its header and its source.

@@ -877,6 +877,61 @@ def bsseval_scores(coh: torch.Tensor, coh_all: torch.Tensor, criterion=None):
     return (sdr.float(), sir.float(), sar.float(), perm, sd.float(), si.float())
 
 
+# ----------------------------------------------------------------------------- PITSDR
+# SI-SDR and SNR of every (source, estimate) pair of a mixture and the assignment (not in the
+# reference; engine: csrc/pitsdr.hip, definition: include/fsem.h "PITSDR"), float64 torch ops on the
+# whole batch: differentiable with respect to the estimates by torch's own autograd.
+PITSDR_MAX_SOURCES = 4
+PITSDR_CRITERIA = {None: 0, "SI-SDR": 1, "SNR": 2}
+
+
+def pitsdr(sources: torch.Tensor, estimates: torch.Tensor, lengths=None, zero_mean: bool = False, criterion=None):
+    """[B, S, L] sources, [B, E, L] estimates -> (si_mat, snr_mat [B, S, E] float64, perm [B, E] int32).
+    ``lengths``: [B] ints, mixture b holds lengths[b] samples.  The gradient of a NaN or +-inf entry
+    is whatever autograd makes of it (the engine leaves such pairs out)."""
+    import itertools
+    if criterion not in PITSDR_CRITERIA:
+        raise ValueError(f"permutation must be one of {list(PITSDR_CRITERIA)}, not {criterion!r}")
+    B, S, L = sources.shape
+    E = estimates.shape[1]
+    s, h = sources.to(torch.float64), estimates.to(torch.float64)
+    n = torch.full((B,), L, dtype=torch.int64) if lengths is None else torch.as_tensor(lengths).to(torch.int64)
+    n = n.clamp(0, L)
+    keep = (torch.arange(L)[None, :] < n[:, None])[:, None, :]  # [B, 1, L]
+    zero = torch.zeros((), dtype=torch.float64)
+    s, h = torch.where(keep, s, zero), torch.where(keep, h, zero)
+    bad = ~(torch.isfinite(s).all(2).all(1) & torch.isfinite(h).all(2).all(1)) | (n == 0)
+    dd = torch.stack([(h - s[:, i:i + 1]).square().sum(2) for i in range(S)], 1)  # [B, S, E]
+    snr = 10 * torch.log10(s.square().sum(2)[:, :, None] / dd)
+    if zero_mean:
+        cnt = n.clamp(min=1)[:, None, None]
+        s = torch.where(keep, s - s.sum(2, keepdim=True) / cnt, zero)
+        h = torch.where(keep, h - h.sum(2, keepdim=True) / cnt, zero)
+    ss, hh = s.square().sum(2)[:, :, None], h.square().sum(2)[:, None, :]
+    sh = torch.einsum("bil,bel->bie", s, h)
+    tt = sh / ss * sh
+    si = 10 * torch.log10(tt / (hh - tt).clamp_min(0))
+    nan = torch.full((), float("nan"), dtype=torch.float64)
+    si = torch.where(dd == 0, torch.full((), float("inf"), dtype=torch.float64), si)
+    si = torch.where((ss == 0) | (hh == 0) | bad[:, None, None], nan, si)
+    snr = torch.where(bad[:, None, None], nan, snr)
+    perm = torch.arange(E, dtype=torch.int32).repeat(B, 1)
+    if criterion is not None and S == E:
+        mat = (si if criterion == "SI-SDR" else snr).detach()
+        ok = ~torch.isnan(mat).flatten(1).any(1)
+        crit = mat.tolist()
+        for m in range(B):
+            if not bool(ok[m]):
+                continue
+            best = None
+            for p in itertools.permutations(range(S)):
+                v = sum(crit[m][p[e]][e] for e in range(S)) / S
+                if best is None or v > best:
+                    best, arg = v, p
+            perm[m] = torch.tensor(arg, dtype=torch.int32)
+    return si, snr, perm
+
+
 # ----------------------------------------------------------------------------- Composite family
 # CSIG, CBAK, COVL with LLR and WSS (Hu & Loizou 2008; not in the reference; engine:
 # csrc/composite.hip, definitions: include/fsem_composite.h), float64, all frames of a chunk of

@@ -97,6 +97,13 @@ SIGNATURES = {
                                          _vp]),
     "fsem_bsseval_scores_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp]),
+    "fsem_pitsdr_max_sources": (ctypes.c_int, []),
+    "fsem_pitsdr_chunk": (_c_i64, [_c_i32]),
+    "fsem_pitsdr_sums_doubles": (_c_i64, [_c_i32, _c_i32, _c_i64, _c_i32]),
+    "fsem_pitsdr_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i32, _c_i32, _c_i64, _c_i64, _vp, _c_i32, _c_i32, _c_i32,
+                                        _vp, _vp, _vp, _vp, _vp]),
+    "fsem_pitsdr_grad_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i32, _c_i32, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp,
+                                             _vp, _vp, _c_i64, _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

@@ -63,7 +63,7 @@ extern "C" {
 #define FSEM_ERATE -5         /* unsupported sample-rate pair (see resampling)      */
 
 const char *fsem_strerror(int code);
-/* (fsem_spectral_*, fsem_srmr_* and fsem_bsseval_* joined at ABI 11 without a bump: entries that take no workspace
+/* (fsem_spectral_*, fsem_srmr_*, fsem_bsseval_* and fsem_pitsdr_* joined at ABI 11 without a bump: entries that take no workspace
  * add to the set and change no existing entry, workspace size or layout.) */
 int fsem_version(void);  /* 11: + fsem_sdr_*; 10: + fsem_pesq_wb_frames_f32; 9: + fsem_pesq_bad_intervals_*, fsem_pesq_pool_f32; 8: + fsem_time_align_p862_*; 7: + fsem_host_buffer_mapped; 6: + fsem_build_id; 5: + fsem_time_align_utt_*; 4: + fsem_pre_emphasize_f32; 3: time alignment, distances */
 /* Content hash (16 hex digits) of the sources, headers and compile flags this library was built
@@ -559,6 +559,68 @@ int fsem_bsseval_f32(const float *src, const float *est, int64_t batch, int32_t 
 int fsem_bsseval_scores_f32(const double *coh, const double *coh_all, int64_t batch, int32_t n_src, int32_t n_est,
                             int32_t criterion, float *sdr, float *sir, float *sar, int32_t *perm, float *sdr_mat,
                             float *sir_mat, void *stream);
+
+/* ---------------------------------------------------------------- PITSDR (SI-SDR and SNR of mixtures, with gradients)
+ * The scale-invariant SDR and the SNR of every estimate against every source of a mixture, the best
+ * assignment, and the gradient of both matrices with respect to the estimates.  An extension: the
+ * reference has no such metric.  Rows are scored at their own sample_rate (no resampling); 0-based.
+ *
+ * A mixture b has S sources s_i (i < S <= 4), E estimates h_e (e < E <= S) and n = lengths[b] samples.
+ *  - Pair scores.  SNR[i, e] = 10 log10(sum s_i^2 / sum (h_e - s_i)^2).  SI-SDR[i, e] is si_sdr of "SDR"
+ *    above for the pair (s_i, h_e), zero_mean and every NaN / +-inf rule included.  All sums in double
+ *    (products of float32 samples are exact there).
+ *  - Non-finite samples.  A mixture with a non-finite sample among its (S + E) n, or with n == 0, is NaN
+ *    in every entry of both matrices (perm: the identity); other mixtures are unaffected.
+ *  - Assignment.  With criterion 1 (SI-SDR) or 2 (SNR), E == S and no NaN in the mixture's criterion
+ *    matrix: over the S! assignments p (estimate e <-> source p[e]) in itertools.permutations order, the
+ *    one with the largest mean over e of the matrix entry [p[e], e] (the double values, summed over
+ *    ascending e, divided by S); equal means keep the earlier assignment, a NaN mean (+inf and -inf
+ *    entries) never wins.  Otherwise p[e] = e.  perm[b, e] = p[e].
+ *  - Gradient.  With k = 20 / ln 10 and incoming gradients G_si, G_snr [batch, S, E] of the two matrices,
+ *      grad[b, e, t] = sum_i A[i, e] s_i[t] + C[e] h_e[t] + K[e]  for t < n, 0 for n <= t < length
+ *      A[i, e] = k G_si[i, e] (1 / sh + sh / (ss nn)) + k G_snr[i, e] / dd
+ *      C[e]    = -k sum_i (G_si[i, e] / nn + G_snr[i, e] / dd)
+ *      K[e]    = -sum_i A_si[i, e] mean(s_i) - C_si[e] mean(h_e)  with zero_mean (the SI-SDR terms of A
+ *                and C alone), else 0
+ *    with ss = sum s_i^2, sh = sum s_i h_e, nn = sum h_e^2 - sh^2 / ss (the centred sums with zero_mean)
+ *    and dd = sum (h_e - s_i)^2.  A pair's SI-SDR (SNR) terms are left out when its SI-SDR (SNR) is not
+ *    finite; a NaN mixture's gradient is zero.  A, C and K are formed in double from the forward's
+ *    totals and rounded to float32; the sum over i (ascending, K first, C h last) is float32 FMAs.
+ *
+ *   src, est : [batch, n_src, length] and [batch, n_est, length] float32; source row (b, i) starts at
+ *              src + (b n_src + i) ld, estimate row (b, e) at est + (b n_est + e) ld.  16-byte loads
+ *              where both bases are 16-byte aligned and ld % 4 == 0 (only inside the first n samples),
+ *              4-byte loads otherwise: the same results.  No sample past n is read.
+ *   lengths  : NULL or [batch] int32, one length per MIXTURE (Conventions)
+ *   criterion: 0 none, 1 SI-SDR, 2 SNR
+ *   sums     : [batch, fsem_pitsdr_sums_doubles(n_src, n_est, length, sample_rate)] float64, the entries'
+ *              only scratch, owned by the caller.  A mixture's block: the totals, then one record per
+ *              chunk of fsem_pitsdr_chunk samples, each ss[S], hh[E], s1[S], h1[E], sh[S E], dd[S E]
+ *              (pair (i, e) at i E + e; s1, h1 the plain sums).  fsem_pitsdr_f32 leaves the totals
+ *              there; fsem_pitsdr_grad_f32 reads them (same batch, shape, length and lengths).
+ *   si_mat, snr_mat : [batch, n_src, n_est] float32;  perm : [batch, n_est] int32
+ *   g_si, g_snr : [batch, n_src, n_est] float32
+ *   grad     : [batch, n_est, length] float32, row (b, e) at grad + (b n_est + e) grad_ld; every one of
+ *              the `length` elements of each row is written (16-byte stores where src, est and grad are
+ *              16-byte aligned and ld % 4 == grad_ld % 4 == 0)
+ * Order of the sums: per chunk, thread t of 256 adds the float4s t, t + 256, ... in ascending order,
+ * the wave's 64 values by a fixed exchange, the four waves as ((w0 + w1) + w2) + w3; the chunks in
+ * ascending order.  No atomics, no hidden allocation.  A mixture's outputs are bitwise the same
+ * whatever the batch size, the mixture's position, `length`, `ld`, the loads' width and the stream.
+ * FSEM_EINVAL before any launch for null pointers (lengths may be NULL), batch < 0, n_src outside
+ * 1 ... 4, n_est outside 1 ... n_src, length < 1, length > 2^29, ld < length, grad_ld < length, a criterion
+ * outside 0 ... 2; then FSEM_ERATE for a sample_rate outside 4000 ... 192000 (the queries return 0).
+ * batch == 0 is FSEM_OK with nothing launched.
+ */
+int fsem_pitsdr_max_sources(void);                /* 4 (host query) */
+int64_t fsem_pitsdr_chunk(int32_t sample_rate);   /* samples per chunk: 8192 at every supported rate */
+int64_t fsem_pitsdr_sums_doubles(int32_t n_src, int32_t n_est, int64_t length, int32_t sample_rate);  /* per mixture: (2 S + 2 E + 2 S E) (1 + chunks); 0 for refused arguments */
+int fsem_pitsdr_f32(const float *src, const float *est, int64_t batch, int32_t n_src, int32_t n_est, int64_t length,
+                    int64_t ld, const int32_t *lengths, int32_t sample_rate, int32_t zero_mean, int32_t criterion,
+                    double *sums, float *si_mat, float *snr_mat, int32_t *perm, void *stream);
+int fsem_pitsdr_grad_f32(const float *src, const float *est, int64_t batch, int32_t n_src, int32_t n_est,
+                         int64_t length, int64_t ld, const int32_t *lengths, int32_t zero_mean, const double *sums,
+                         const float *g_si, const float *g_snr, float *grad, int64_t grad_ld, void *stream);
 
 #ifdef __cplusplus
 }
