@@ -4,6 +4,11 @@ Runs at 10 kHz internally (STOI.py:9).  ``use_gpu=True``: libfsem's gfx950 kerne
 (``fsem_stoi_f32``) with the 16 -> 10 kHz resampler fused into them (the reference
 resamples in BaseMetric.prepare_audio, base.py:19-20; same arithmetic), one device->host
 copy of the scores.  ``use_gpu=False``: the package's CPU implementation.
+
+``differentiable_scores`` and ``loss`` are the same scores with the gradient with respect to the
+denoised rows (include/fsem.h, "STOI with gradients"): on the engine
+``fsem_stoi_state_f32`` forward and ``fsem_stoi_grad_f32`` backward (csrc/stoi_grad.hip), in CPU mode
+``_cpu.stoi`` in float64 under torch's own autograd.
 """
 from __future__ import annotations
 
@@ -15,6 +20,57 @@ import torch
 from . import _cpu, _native
 from .base import BaseMetric, as_rows, check_row_rate, device_lengths, noisy_shape, same_device, zero_tail
 from .batching import resampled_lengths
+
+
+class _EngineScores(torch.autograd.Function):
+    """(stoi, estoi [B] float32, segments [B] int32) of CUDA rows by the engine (fsem_stoi_state_f32, the
+    kernels of fsem_stoi_f32 on a state of this call's own); the backward is fsem_stoi_grad_f32 on that
+    state.  ``clean`` and ``noisy`` are the rows as the engine reads them (float32, one stride, readable
+    to ceil4(L)); the gradient comes back [B, L]."""
+
+    @staticmethod
+    def forward(ctx, noisy, clean, lens, L, sr):
+        lib = _native.load()
+        B, dev = clean.shape[0], clean.device
+        s = torch.empty(B, dtype=torch.float32, device=dev)
+        e = torch.empty(B, dtype=torch.float32, device=dev)
+        seg = torch.zeros(B, dtype=torch.int32, device=dev)
+        ctx.mark_non_differentiable(seg)
+        ctx.shape = (B, L, noisy.shape[1])
+        ctx.state = None
+        if B == 0:
+            return s, e, seg
+        nfloats = lib.fsem_stoi_state_floats(B, L, sr)
+        if nfloats == 0:
+            raise NotImplementedError(f"unsupported sample rate {sr}: its resampling filter to 10 kHz would be longer "
+                                      "than 8192 taps (include/fsem.h, FSEM_ERATE)")
+        state = torch.empty(nfloats, dtype=torch.float32, device=dev)  # (not the shared workspace: it must outlive the call)
+        rc = lib.fsem_stoi_state_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
+                                     lens.data_ptr() if lens is not None else None, sr, s.data_ptr(), e.data_ptr(),
+                                     seg.data_ptr(), state.data_ptr(), _native.stream_handle(dev))
+        if rc == _native.FSEM_ESHORT:
+            raise RuntimeError("STOI input shorter than one 256-sample frame at 10 kHz")
+        _native.check(rc, "STOI")
+        ctx.state, ctx.noisy, ctx.lens, ctx.sr = state, noisy, lens, sr
+        return s, e, seg
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_s, g_e, _g_seg):
+        B, L, width = ctx.shape
+        if ctx.state is None:
+            return torch.zeros(B, width, dtype=torch.float32, device=g_s.device), None, None, None, None
+        grad = torch.empty(B, width, dtype=torch.float32, device=g_s.device)  # (the entry writes [:, :L])
+        grad[:, L:] = 0
+        g_s = g_s.to(torch.float32).contiguous()
+        g_e = g_e.to(torch.float32).contiguous()
+        lens = ctx.lens
+        rc = _native.load().fsem_stoi_grad_f32(
+            ctx.noisy.data_ptr(), B, L, ctx.noisy.stride(0), lens.data_ptr() if lens is not None else None, ctx.sr,
+            ctx.state.data_ptr(), g_s.data_ptr(), g_e.data_ptr(), grad.data_ptr(), grad.stride(0),
+            _native.stream_handle(g_s.device))
+        _native.check(rc, "STOI backward")
+        return grad, None, None, None, None
 
 
 class STOI(BaseMetric):
@@ -173,6 +229,7 @@ class STOI(BaseMetric):
         same_device(clean, noisy)
         B, L = clean.shape
         if not clean.is_cuda:
+            clean, noisy = clean.detach(), noisy.detach()  # scores are detached, as the engine's (differentiable_scores)
             if lengths is not None:
                 lens = device_lengths(lengths, B, L, "cpu")
                 if sr != self.EXPECTED_SAMPLING_RATE:
@@ -204,6 +261,90 @@ class STOI(BaseMetric):
             raise RuntimeError("STOI input shorter than one 256-sample frame at 10 kHz")
         _native.check(rc, "STOI")
         return s, e
+
+    # ------------------------------------------------------------------ scores to train against
+    KEYS_LOSS = ("STOI", "ESTOI")
+
+    def _differentiable(self, clean_speech, denoised_speech, sample_rate, lengths):
+        """(stoi [B], estoi [B], segments [B]) with the graph to ``denoised_speech`` (include/fsem.h, "STOI with
+        gradients"): float32 from the engine on CUDA rows, float64 from ``_cpu.stoi`` under torch's own
+        autograd on host rows."""
+        if self._fanout is not None:
+            raise NotImplementedError("STOI: devices= is not supported with gradients (the multi-device fan-out "
+                                      "returns detached scores)")
+        sr = check_row_rate(self, sample_rate)
+        clean, noisy = torch.as_tensor(clean_speech), torch.as_tensor(denoised_speech)
+        if clean.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("STOI: the clean rows are constants; gradients with respect to `clean_speech` "
+                                      "are not supported (detach them)")
+        clean, noisy = torch.atleast_2d(clean.detach()), torch.atleast_2d(noisy)
+        if noisy.shape != clean.shape or clean.dim() != 2:
+            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
+        same_device(clean, noisy)
+        B, L = clean.shape
+        if not clean.is_cuda:
+            return self._differentiable_cpu(clean, noisy, sr, lengths)
+        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
+        clean, rows = as_rows(clean), noisy.to(torch.float32)  # (autograd casts the gradient back)
+        if rows.stride(-1) != 1 or rows.stride(0) < L:
+            rows = rows.contiguous()
+        if clean.stride(0) != rows.stride(0) or L % 4:
+            # rows must be readable up to ceil4(L) floats (include/fsem.h): pad odd lengths
+            pad = (-L) % 4
+            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
+            rows = torch.nn.functional.pad(rows, (0, pad)).contiguous()
+        return _EngineScores.apply(rows, clean, lens, L, sr)
+
+    def _differentiable_cpu(self, clean, noisy, sr: int, lengths):
+        B, L = clean.shape
+        lens = device_lengths(lengths, B, L, "cpu").tolist() if lengths is not None else [L] * B
+        nan = torch.full((1,), float("nan"), dtype=torch.float64)
+        out_s, out_e, segs = [], [], []
+        for b in range(B):  # (a plain loop: each row's graph hangs on its own slice of `noisy`)
+            n = int(lens[b])
+            c10 = _cpu.resample64(clean[b:b + 1, :n], sr, self.EXPECTED_SAMPLING_RATE)
+            seg = int(_cpu.stoi_segments(c10)[0]) if c10.shape[1] >= 256 else 0
+            segs.append(seg)
+            row = noisy[b:b + 1, :n]
+            if seg == 0:
+                s, e = nan, nan
+            elif not bool(torch.isfinite(row.detach()).all()):
+                with torch.no_grad():  # a non-finite sample: the scores, no gradient (a zero row)
+                    s, e = _cpu.stoi(c10, _cpu.resample64(row, sr, self.EXPECTED_SAMPLING_RATE))
+            else:
+                s, e = _cpu.stoi(c10, _cpu.resample64(row, sr, self.EXPECTED_SAMPLING_RATE))
+            out_s.append(s)
+            out_e.append(e)
+        if not B:
+            return torch.zeros(0, dtype=torch.float64), torch.zeros(0, dtype=torch.float64), torch.zeros(0, dtype=torch.int32)
+        return torch.cat(out_s), torch.cat(out_e), torch.tensor(segs, dtype=torch.int32)
+
+    def differentiable_scores(self, clean_speech: torch.Tensor, denoised_speech: torch.Tensor,
+                              sample_rate: int | None = None, lengths=None):
+        """(stoi [B], estoi [B]) as ``scores``, carrying the gradient with respect to ``denoised_speech``:
+        float32 and bitwise ``scores()`` on the engine (``fsem_stoi_state_f32`` / ``fsem_stoi_grad_f32``),
+        float64 in CPU mode.  The clean rows are constants; a row without a segment (NaN) or with a
+        non-finite sample gets a zero gradient; a zero band envelope takes the subgradient 0."""
+        s, e, _ = self._differentiable(clean_speech, denoised_speech, sample_rate, lengths)
+        return s, e
+
+    def loss(self, clean_speech: torch.Tensor, denoised_speech: torch.Tensor, sample_rate: int | None = None,
+             lengths=None, key: str = "ESTOI") -> torch.Tensor:
+        """-mean of ``key`` ("STOI" or "ESTOI") over the rows that have a 30-frame segment: a scalar that
+        carries the gradient with respect to ``denoised_speech``.  With no such row: the warning of the
+        drop-in call and a zero with a zero gradient."""
+        if key not in self.KEYS_LOSS:
+            raise ValueError(f"key must be one of {list(self.KEYS_LOSS)}, not {key!r}")
+        s, e, seg = self._differentiable(clean_speech, denoised_speech, sample_rate, lengths)
+        score = s if key == "STOI" else e
+        scored = seg.to(score.device) > 0
+        count = int(scored.sum())
+        total = torch.where(scored, score, torch.zeros((), dtype=score.dtype, device=score.device)).sum()
+        if count == 0:
+            warnings.warn("Not enough non-silent frames. Please check your sound files", RuntimeWarning, stacklevel=2)
+            # (an empty sum of the estimate: a zero on the graph, whose gradient is zero)
+            return total + torch.as_tensor(denoised_speech).reshape(-1)[:0].sum().to(total)
+        return -total / count
 
     def _finish(self, stois: torch.Tensor, estois: torch.Tensor) -> list[dict[str, float]]:
         t = torch.stack([stois.float(), estois.float()])

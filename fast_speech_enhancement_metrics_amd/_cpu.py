@@ -198,8 +198,50 @@ def _estoi_norm(seg: torch.Tensor) -> torch.Tensor:
     return a / q.sqrt()
 
 
+def stoi_segments(clean: torch.Tensor) -> torch.Tensor:
+    """[B] int64: the 30-frame segments of each 10 kHz clean row, kept frames - 31 (0: the row scores NaN)."""
+    x = clean.detach().to(torch.float64)
+    if x.shape[1] < 256:
+        return torch.zeros(x.shape[0], dtype=torch.int64)
+    e = 20 * torch.log10((x.unfold(1, 256, 128) * _SW).norm(dim=2) + 1e-9)
+    keep = (e.amax(1, keepdim=True) - 40 - e) < 0
+    return (keep.sum(1) - 31).clamp(min=0)
+
+
+def resample64(x: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
+    """[B, n] -> [B, ceil(new n / orig)] float64: the package's resampler (resample.sinc_kernel's float32
+    taps) applied in float64, differentiable under autograd."""
+    x = x.to(torch.float64)
+    if int(orig_freq) == int(new_freq):
+        return x
+    from .resample import sinc_kernel
+    kern, width, orig, new = sinc_kernel(orig_freq, new_freq)
+    n = x.shape[1]
+    xp = torch.nn.functional.pad(x, (width, width + orig))
+    res = torch.nn.functional.conv1d(xp[:, None], kern.to(torch.float64)[:, None], stride=orig)
+    return res.transpose(1, 2).reshape(x.shape[0], -1)[:, :-(-new * n // orig)]
+
+
+class _Sqrt0(torch.autograd.Function):
+    """torch.sqrt with the subgradient 0 at 0 (torch's own derivative there is inf, and NaN once it meets
+    a zero): the band envelopes of an all-zero estimate get a zero, finite gradient.  Same values."""
+
+    @staticmethod
+    def forward(ctx, p):
+        s = torch.sqrt(p)
+        ctx.save_for_backward(s)
+        return s
+
+    @staticmethod
+    def backward(ctx, g):
+        s, = ctx.saved_tensors
+        return torch.where(s > 0, g / (2 * s), torch.zeros_like(g))
+
+
 def stoi(clean: torch.Tensor, noisy: torch.Tensor):
-    """[B, L10] 10 kHz -> (stoi [B], estoi [B]) float64; NaN where no 30-frame segment exists."""
+    """[B, L10] 10 kHz -> (stoi [B], estoi [B]) float64; NaN where no 30-frame segment exists.
+    Differentiable with respect to ``noisy`` under autograd (the selection of frames is the clean
+    rows'), with the subgradient 0 where a band envelope is 0."""
     B = clean.shape[0]
     out_s = torch.full((B,), float("nan"), dtype=torch.float64)
     out_e = torch.full((B,), float("nan"), dtype=torch.float64)
@@ -227,7 +269,7 @@ def stoi(clean: torch.Tensor, noisy: torch.Tensor):
         oy.index_add_(0, idx, ky.reshape(-1))
         sp = torch.stft(torch.stack([ox, oy]), n_fft=512, hop_length=128, win_length=512, window=win512,
                         center=False, return_complex=True).abs().square()            # [2, 257, T]
-        tob = torch.sqrt(torch.matmul(_OBM, sp))                                      # [2, 15, T]
+        tob = _Sqrt0.apply(torch.matmul(_OBM, sp))                                    # [2, 15, T]
         segs = tob.unfold(2, 30, 1)[:, :, :nseg]                                      # [2, 15, S, 30]
         cx, cy = segs[0].transpose(0, 1), segs[1].transpose(0, 1)                     # [S, 15, 30]
         alpha = cx.norm(dim=2, keepdim=True) / (cy.norm(dim=2, keepdim=True) + 1e-9)

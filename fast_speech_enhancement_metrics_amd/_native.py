@@ -104,6 +104,9 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _vp, _vp]),
     "fsem_pitsdr_grad_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i32, _c_i32, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp,
                                              _vp, _vp, _c_i64, _vp]),
+    "fsem_stoi_state_floats": (_c_i64, [_c_i64, _c_i64, _c_i32]),
+    "fsem_stoi_state_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp]),
+    "fsem_stoi_grad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _vp, _c_i64, _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

@@ -20,42 +20,11 @@
 //                lane per segment, band envelopes staged in LDS (no 30x materialisation).
 #include <algorithm>
 
-#include "fsem_fft.h"
 #include "fsem_internal.h"
-#include "fsem_resample.h"
-#include "fsem_vad.h"
+#include "fsem_stoi.h"
 
 namespace fsem {
 namespace stoi {
-
-constexpr int NB = 15;     // one-third octave bands
-constexpr int NSEG = 30;   // frames per segment
-constexpr int VF = 64;     // VAD frames per workgroup
-#ifndef FSEM_TOB_TF
-#define FSEM_TOB_TF 32
-#endif
-constexpr int TF = FSEM_TOB_TF;  // STFT frames per workgroup
-constexpr float kClip = 1.0f + 5.62341325190349f;  // 1 + 10^(-beta/20), beta = -15 (STOI.py:136-137)
-
-// Per-row lengths: row b holds lens[b] input samples (clamped to [0, ncap]) when lens is
-// given, else ncap.  Its 10 kHz length is that of the reference's resampler on the unpadded
-// row, ceil(n * nw / orig) (torchaudio Resample, base.py:20), and its VAD frame count
-// 1 + (L10 - 256) / 128 (STOI.py:92-94).
-struct Rows {
-  const int32_t *lens;
-  int64_t ncap;
-  int orig, nw;  // reduced rate pair (1, 1 for 10 kHz input)
-  __device__ __forceinline__ int64_t n(int64_t b) const {
-    if (!lens) return ncap;
-    const int64_t v = lens[b];
-    return v < 0 ? 0 : (v > ncap ? ncap : v);
-  }
-  __device__ __forceinline__ int64_t l10(int64_t b) const { return (n(b) * nw + orig - 1) / orig; }
-  __device__ __forceinline__ int nv(int64_t b) const {
-    const int64_t L10 = l10(b);
-    return L10 >= 256 ? (int)((L10 - 256) / 128 + 1) : 0;
-  }
-};
 
 struct Src {
   const float *x;  // input row base (clean or denoised)
@@ -302,34 +271,6 @@ __device__ unsigned long long g_tob_stamps[kTobStampBlocks][4];
   } while (0)
 #endif
 
-// Peak biased float exponents of a wave's clean and denoised samples (0: all zero or
-// denormal), packed (clean << 16 | denoised): per-lane maxima, then a DPP reduction (row
-// rotations, row broadcasts) with a packed 16-bit max -- both signals per instruction, no LDS --
-// whose last lane holds the wave's maxima (uniform result).
-__device__ __forceinline__ uint32_t peak_exponents(float c0, float c1, float c2, float c3, float d0, float d1,
-                                                   float d2, float d3) {
-  typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-  // exponent field of the largest magnitude: a float max over |x| (abs source modifiers, max3)
-  auto mx4 = [](float a, float b, float c, float d) {
-    return __float_as_uint(__builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b)),
-                                           __builtin_fmaxf(__builtin_fabsf(c), __builtin_fabsf(d))));
-  };
-  const uint32_t mc = mx4(c0, c1, c2, c3), md = mx4(d0, d1, d2, d3);
-  uint32_t e = ((mc >> 7) & 0xffff0000u) | (md >> 23);
-  auto pmax = [](uint32_t x, uint32_t y) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2, x), __builtin_bit_cast(us2, y)));
-  };
-  e = pmax(e, dpp_mov<0x121>(e));  // row_ror:1
-  e = pmax(e, dpp_mov<0x122>(e));  // row_ror:2
-  e = pmax(e, dpp_mov<0x124>(e));  // row_ror:4
-  e = pmax(e, dpp_mov<0x128>(e));  // row_ror:8 -> every lane holds its row's maxima
-  // rows 1 and 3 take rows 0 and 2 (row_bcast:15), rows 2 and 3 take lane 31 (row_bcast:31);
-  // rows outside the mask read 0, the identity of the max
-  e = pmax(e, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e, 0x142, 0xA, 0xF, false));
-  e = pmax(e, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e, 0x143, 0xC, 0xF, false));
-  return __builtin_amdgcn_readlane(e, 63);
-}
-
 // Powers of one transform in the wave's exchange area, bin k of frame a at tob_pw(k), of frame b
 // at TOB_PB + tob_pw(k): bins from 128 on 3 words further, which makes the band sums' 12 piece
 // reads (lane l reads its piece start + i) 2-way instead of 3-way bank conflicts in each 32-lane
@@ -545,13 +486,9 @@ __global__ void __launch_bounds__(64 * TOB_WAVES)
 // v_pk_add_f32 / v_pk_mul_f32: twice the v_fma_f32 rate on gfx950).  The per-lane row
 // statistics of the ESTOI time normalisation stay in registers (uniform-index writes from the
 // rolled band loop).
-#ifndef FSEM_SEG_T
-#define FSEM_SEG_T 256
-#endif
 #ifndef FSEM_SEG_OCC
 #define FSEM_SEG_OCC 3
 #endif
-constexpr int SEG_T = FSEM_SEG_T;
 constexpr int SEG_WAVES = SEG_T / 64;
 typedef float f2 __attribute__((ext_vector_type(2)));
 __global__ void __launch_bounds__(SEG_T, FSEM_SEG_OCC)
@@ -745,58 +682,6 @@ __global__ void __launch_bounds__(256)
   estoi_out[b] = (float)(et / NSEG / S);
 }
 
-// segment blocks per row of a tob buffer with tmax frames (S <= tmax - 29)
-inline int seg_blocks(int64_t tmax) { return tmax > 29 ? (int)((tmax - 29 + SEG_T - 1) / SEG_T) : 1; }
-
-struct Geometry {
-  int64_t L10;
-  int NV, nv_ld, tmax;
-  int64_t v_ld;  // VAD quarter sums per row (float2)
-  int64_t y_ld;
-  bool direct;
-  int mode;
-};
-
-inline int make_geometry(int64_t length, int32_t sr, Geometry *g, ResampleKernel *rk) {
-  g->direct = (sr == 10000);
-  if (g->direct) {
-    g->L10 = length;
-    rk->orig = rk->nw = 1;
-    rk->taps = 1;
-    rk->width = 0;
-  } else {
-    const int rc = make_resample_kernel(sr, 10000, rk);
-    if (rc != FSEM_OK) return rc;
-    g->L10 = (rk->nw * length + rk->orig - 1) / rk->orig;
-  }
-  g->NV = g->L10 >= 256 ? (int)((g->L10 - 256) / 128 + 1) : 0;
-  g->nv_ld = (int)align_up((size_t)(g->NV > 0 ? g->NV : 1), 64);
-  g->v_ld = vad_ld(g->L10);
-  g->tmax = g->NV > 2 ? g->NV - 2 : 1;
-  g->y_ld = (int64_t)align_up((size_t)g->L10, 64);
-  g->mode = g->direct ? 1 : ((sr == 16000) ? 0 : 2);
-  return FSEM_OK;
-}
-
-// The STOI workspace (Arena, fsem_common.h).
-struct Ws {
-  float2 *vad;
-  int *idx, *kept;
-  float *tob;
-  double *part;
-  float *y10;
-};
-inline Ws layout(Arena &a, int64_t B, const Geometry &g) {
-  Ws w;
-  w.vad = a.take<float2>((size_t)B * (size_t)g.v_ld);                 // VAD quarter sums
-  w.idx = a.take<int>((size_t)B * g.nv_ld);                           // kept indices
-  w.kept = a.take<int>((size_t)B);                                    // kept counts
-  w.tob = a.take<float>((size_t)(2 * B) * NB * (size_t)g.tmax);       // tob
-  w.part = a.take<double>(2 * (size_t)B * (size_t)seg_blocks(g.tmax));  // segment block sums
-  w.y10 = a.take<float>((size_t)(2 * B) * (size_t)g.y_ld);            // 10 kHz signals
-  return w;
-}
-
 // Everything after the clean frame energies: selection, band envelopes, segments.
 inline int run_seg(int64_t B, const float *tob, int64_t tmax, const int *kept, double *part, float *stoi_out,
                    float *estoi_out, hipStream_t st) {
@@ -826,9 +711,9 @@ inline int run_tail(int64_t B, const Geometry &g, const Rows &rows, const float 
   return FSEM_OK;
 }
 
-inline int run(const float *ref, const float *deg, int64_t B, int64_t length, int64_t ld,
-               const int32_t *lengths, int32_t sr, float *stoi_out, float *estoi_out, int32_t *kept_out,
-               float *tob_out, int64_t tob_ld, void *ws, size_t ws_size, hipStream_t st) {
+int run(const float *ref, const float *deg, int64_t B, int64_t length, int64_t ld,
+        const int32_t *lengths, int32_t sr, float *stoi_out, float *estoi_out, int32_t *kept_out,
+        float *tob_out, int64_t tob_ld, void *ws, size_t ws_size, hipStream_t st) {
   Geometry g;
   ResampleKernel rk;
   int rc = make_geometry(length, sr, &g, &rk);

@@ -622,6 +622,57 @@ int fsem_pitsdr_grad_f32(const float *src, const float *est, int64_t batch, int3
                          int64_t length, int64_t ld, const int32_t *lengths, int32_t zero_mean, const double *sums,
                          const float *g_si, const float *g_snr, float *grad, int64_t grad_ld, void *stream);
 
+/* ---------------------------------------------------------------- STOI with gradients
+ * STOI and ESTOI of fsem_stoi_f32 as a function to train against: the scores, and the gradient of
+ *   L = sum_b (g_stoi[b] STOI_b + g_estoi[b] ESTOI_b)
+ * with respect to the denoised rows at the input rate.  (Joined at ABI 11 without a bump, as above.)
+ * The function differentiated is STOI above with the reference's 1e-12 * randn terms in expectation, as
+ * the forward takes them: the resampler, the selection of frames by the CLEAN rows' energies (a constant),
+ * the overlap-add of the kept frames, the STFT, the band envelopes sqrt(sum |Z|^2), the segments'
+ * equalisation alpha = |x| / (|y| + 1e-9), the clipping min(alpha y, (1 + 10^(15/20)) x), both
+ * normalisations with their N 1e-24 regularisers and the (14/15) sum 1e-24 / n2 term of the band
+ * normalisation, all differentiated as written.
+ *  - Clean rows are constants: no gradient with respect to ref.
+ *  - A row without a 30-frame segment (scores NaN) and a row with a non-finite denoised sample among its
+ *    lengths[b] samples get a gradient row of exact zeros; no other row is touched.
+ *  - Where a denoised band envelope is exactly 0 (e.g. an all-zero row) the square root has no
+ *    derivative: the subgradient 0 is taken there, so an all-zero estimate has a zero, finite gradient.
+ *    Likewise |y| = 0 in alpha.  At the clipping's min the side alpha y < (1 + 10^(15/20)) x is the
+ *    denoised one (ties have measure zero).
+ *  - With lengths, grad[b, lengths[b] .. length) is zero and row b's gradient is that of the unpadded row.
+ *  - A row's gradient does not depend on the batch it is in, and two calls give the same bits: every
+ *    sum is a gather or a store-then-sum in a fixed order; no atomics, no hidden allocation.
+ *
+ *   state    : [fsem_stoi_state_floats(batch, length, sample_rate)] float32, owned by the caller, 256-byte
+ *              aligned.  Its head is the workspace of fsem_stoi_f32, laid out as that entry lays it
+ *              out (fsem_stoi_workspace_bytes: per row the VAD sums, the kept frame indices and count, both
+ *              envelope sets [2, 15, tmax], the segment block sums and both 10 kHz rows [2, ceil64(L10)]),
+ *              which fsem_stoi_state_f32 leaves filled; its tail is the backward's scratch: per row one
+ *              flag, the kept position of each frame [ceil64(frames)], the envelope derivatives [ceil((tmax - 29) / 64), 15, 96], the frame derivatives
+ *              [tmax, 256] and, unless sample_rate is 10000, the 10 kHz row's derivative [ceil64(L10)]
+ *              (L10 = ceil(length * 10000 / sample_rate), tmax = (L10 - 256) / 128 - 1): about
+ *              (2 + 0.23 + 2 + 1) L10 * 4 bytes per row beside the forward's (2 + 0.23) L10 * 4,
+ *              e.g. 0.87 MB per 4 s row at 16 kHz, 0.36 MB of it the forward's.
+ *   fsem_stoi_state_f32 : the scores of fsem_stoi_f32, bitwise (the same kernels on the state's head).
+ *              FSEM_ESHORT as there.
+ *   fsem_stoi_grad_f32  : reads the state fsem_stoi_state_f32 left for the same deg, batch, length, ld,
+ *              lengths and sample_rate, writes the tail, and writes every element of grad[b, 0 .. length)
+ *              (row b at grad + b grad_ld).  It may be called again on the same state.
+ *   segments : NULL or [batch] int32: the 30-frame segments of each row (kept frames - 31; 0: the row
+ *              scores NaN and gets no gradient).
+ *   g_stoi, g_estoi : [batch] float32 device arrays.
+ * FSEM_EINVAL before any launch for null pointers (lengths may be NULL), batch < 0, length <= 0,
+ * length > 2^29, ld < length, grad_ld < length; then FSEM_ERATE for a rate without a resampling kernel
+ * (fsem_stoi_state_floats returns 0 for any of these).  batch == 0 is FSEM_OK with nothing launched.
+ */
+int64_t fsem_stoi_state_floats(int64_t batch, int64_t length, int32_t sample_rate);  /* 0 for refused arguments */
+int fsem_stoi_state_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                        const int32_t *lengths, int32_t sample_rate, float *stoi_out, float *estoi_out,
+                        int32_t *segments, float *state, void *stream);
+int fsem_stoi_grad_f32(const float *deg, int64_t batch, int64_t length, int64_t ld, const int32_t *lengths,
+                       int32_t sample_rate, float *state, const float *g_stoi, const float *g_estoi,
+                       float *grad, int64_t grad_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
