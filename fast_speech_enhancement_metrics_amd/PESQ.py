@@ -4,6 +4,11 @@ P.862-like wideband model without time alignment and with IIR level alignment
 (reference PESQ.py:17-23).  ``use_gpu=True``: the whole per-utterance pipeline runs in
 libfsem's gfx950 kernels (``fsem_pesq_wb_f32``) with one device->host copy of the scores;
 ``use_gpu=False``: the package's CPU implementation.
+
+``differentiable_scores`` and ``loss`` are the same scores with the gradient with respect to the
+denoised rows (include/fsem.h, "PESQ with gradients"): on the engine
+``fsem_pesq_state_f32`` forward and ``fsem_pesq_grad_f32`` backward (csrc/pesq_grad.hip), in CPU mode
+``_cpu.pesq_differentiable`` in float64 under torch's own autograd.
 """
 from __future__ import annotations
 
@@ -50,6 +55,51 @@ def _wb_frames(lib, clean: torch.Tensor, noisy: torch.Tensor, lens):
                                               dist.data_ptr(), frames.data_ptr(), ws.data_ptr(), ws.numel(),
                                               _native.stream_handle(clean.device)), "PESQ frames")
     return dist[0], frames
+
+
+class _EngineScores(torch.autograd.Function):
+    """(mos, symmetric distance, asymmetric distance [B] float32) of 16 kHz CUDA rows by the engine
+    (fsem_pesq_state_f32, the kernels of fsem_pesq_wb_frames_f32 on a state of this call's own); the
+    backward is fsem_pesq_grad_f32 on that state.  ``clean`` and ``noisy`` are the rows as the engine
+    reads them (float32, one stride, readable to ceil4(L)); the gradient comes back [B, width]."""
+
+    @staticmethod
+    def forward(ctx, noisy, clean, lens, L):
+        lib = _native.load()
+        B, dev = clean.shape[0], clean.device
+        mos = torch.empty(B, dtype=torch.float32, device=dev)
+        dist = torch.empty(2, B, dtype=torch.float32, device=dev)
+        ctx.shape = (B, L, noisy.shape[1])
+        ctx.state = None
+        if B == 0:
+            return mos, dist[0], dist[1]
+        state = torch.empty(lib.fsem_pesq_state_floats(B, L), dtype=torch.float32, device=dev)  # (outlives the call)
+        rc = lib.fsem_pesq_state_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
+                                     lens.data_ptr() if lens is not None else None, mos.data_ptr(), dist.data_ptr(),
+                                     state.data_ptr(), _native.stream_handle(dev))
+        if rc == _native.FSEM_ESHORT:
+            raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(lib.fsem_pesq_frames(L), 0)} "
+                               "but size is 20")
+        _native.check(rc, "PESQ")
+        ctx.state, ctx.noisy, ctx.lens = state, noisy, lens
+        return mos, dist[0], dist[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_mos, g_sym, g_asym):
+        B, L, width = ctx.shape
+        if ctx.state is None:
+            return torch.zeros(B, width, dtype=torch.float32, device=g_mos.device), None, None, None
+        grad = torch.empty(B, width, dtype=torch.float32, device=g_mos.device)  # (the entry writes [:, :L])
+        grad[:, L:] = 0
+        g = [v.to(torch.float32).contiguous() for v in (g_mos, g_sym, g_asym)]
+        lens = ctx.lens
+        rc = _native.load().fsem_pesq_grad_f32(
+            ctx.noisy.data_ptr(), B, L, ctx.noisy.stride(0), lens.data_ptr() if lens is not None else None,
+            ctx.state.data_ptr(), g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), grad.data_ptr(), grad.stride(0),
+            _native.stream_handle(g_mos.device))
+        _native.check(rc, "PESQ backward")
+        return grad, None, None, None
 
 
 class PESQ(BaseMetric):
@@ -278,6 +328,10 @@ class PESQ(BaseMetric):
         sr = check_row_rate(self, sample_rate)
         if noisy_shape(clean_speech) != noisy_shape(denoised_speech):
             raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
+        if isinstance(clean_speech, torch.Tensor):  # scores are detached (differentiable_scores carries the graph)
+            clean_speech = clean_speech.detach()
+        if isinstance(denoised_speech, torch.Tensor):
+            denoised_speech = denoised_speech.detach()
         aligned = getattr(self, "time_align", False)
         if self.fans_out():
             def shard(c, n, lk):
@@ -333,6 +387,112 @@ class PESQ(BaseMetric):
                                            mos.data_ptr(), ws.data_ptr(), ws.numel(),
                                            _native.stream_handle(clean.device)), "PESQ")
         return mos, delays
+
+    # ------------------------------------------------------------------ scores to train against
+    KEYS_LOSS = ("PESQ", "distance")
+
+    def _differentiable(self, clean_speech, denoised_speech, sample_rate, lengths):
+        """(mos [B], symmetric distance [B], asymmetric distance [B], scored [B] bool) with the graph to
+        ``denoised_speech`` (include/fsem.h, "PESQ with gradients"): float32 from the engine on CUDA rows,
+        float64 from ``_cpu.pesq_differentiable`` under torch's own autograd on host rows.  ``scored``: the
+        row has at least 20 frames."""
+        if self._fanout is not None:
+            raise NotImplementedError("PESQ: devices= is not supported with gradients (the multi-device fan-out "
+                                      "returns detached scores): use one device per process")
+        if getattr(self, "time_align", False):
+            raise NotImplementedError("PESQ: time_align is not supported with gradients (the delay search is not "
+                                      "differentiable): align the rows first (alignment.time_align) and use "
+                                      "PESQ(time_align=False)")
+        sr = check_row_rate(self, sample_rate)
+        clean, noisy = torch.as_tensor(clean_speech), torch.as_tensor(denoised_speech)
+        if clean.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("PESQ: the clean rows are constants; gradients with respect to `clean_speech` "
+                                      "are not supported (detach them)")
+        clean, noisy = torch.atleast_2d(clean.detach()), torch.atleast_2d(noisy)
+        if noisy.shape != clean.shape or clean.dim() != 2:
+            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
+        same_device(clean, noisy)
+        B, L = clean.shape
+        if not clean.is_cuda:
+            return self._differentiable_cpu(clean, noisy, sr, lengths)
+        if sr != self.EXPECTED_SAMPLING_RATE:
+            raise NotImplementedError(f"PESQ: the engine's gradients take rows at 16 kHz, not {sr} Hz: resample the "
+                                      "rows first with differentiable torch ops, or use PESQ(use_gpu=False)")
+        lib = _native.load()
+        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
+        if lib.fsem_pesq_frames(L) < 20 and lens is None:
+            raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(lib.fsem_pesq_frames(L), 0)} "
+                               "but size is 20")
+        clean, rows = as_rows(clean), noisy.to(torch.float32)  # (autograd casts the gradient back)
+        if rows.stride(-1) != 1 or rows.stride(0) < L:
+            rows = rows.contiguous()
+        if clean.stride(0) != rows.stride(0) or L % 4:
+            # rows must be readable up to ceil4(L) floats (include/fsem.h): pad odd lengths
+            pad = (-L) % 4
+            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
+            rows = torch.nn.functional.pad(rows, (0, pad)).contiguous()
+        mos, sym, asym = _EngineScores.apply(rows, clean, lens, L)
+        if lens is None:
+            scored = torch.ones(B, dtype=torch.bool, device=clean.device)
+        else:
+            n = lens.to(torch.int64)
+            scored = (n + n % 256) >= 512 + 19 * 256
+        return mos, sym, asym, scored
+
+    def _differentiable_cpu(self, clean, noisy, sr: int, lengths):
+        B, L = clean.shape
+        lens = device_lengths(lengths, B, L, "cpu").tolist() if lengths is not None else [L] * B
+        rate = self.EXPECTED_SAMPLING_RATE
+        if lengths is None and B:
+            F = _cpu.pesq_frames(_cpu.resample64(clean[:1], sr, rate).shape[1])
+            if F < 20:  # as scores(): the reference's unfold(1, size=20, step=10) fails here (PESQ.py:169)
+                raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(F, 0)} but size is 20")
+        nan = torch.full((1,), float("nan"), dtype=torch.float64)
+        outs, scored = [], []
+        for b in range(B):  # (a plain loop: each row's graph hangs on its own slice of `noisy`)
+            n = int(lens[b])
+            c16 = _cpu.resample64(clean[b:b + 1, :n], sr, rate)
+            ok = _cpu.pesq_frames(c16.shape[1]) >= 20
+            scored.append(ok)
+            row = noisy[b:b + 1, :n]
+            if not ok:
+                outs.append((nan, nan, nan))
+                continue
+            out = _cpu.pesq_differentiable(c16, _cpu.resample64(row, sr, rate))
+            if not bool(torch.isfinite(out[0].detach()).all()):
+                # zero band-pass power or a non-finite sample: the scores, no gradient (a zero row)
+                out = tuple(o.detach() for o in out)
+            outs.append(out)
+        if not B:
+            z = torch.zeros(0, dtype=torch.float64)
+            return z, z.clone(), z.clone(), torch.zeros(0, dtype=torch.bool)
+        return (*(torch.cat([o[i] for o in outs]) for i in range(3)), torch.tensor(scored))
+
+    def differentiable_scores(self, clean_speech: torch.Tensor, denoised_speech: torch.Tensor,
+                              sample_rate: int | None = None, lengths=None) -> torch.Tensor:
+        """MOS [B] as ``scores``, carrying the gradient with respect to ``denoised_speech``: float32 and
+        bitwise ``scores()`` on the engine (``fsem_pesq_state_f32`` / ``fsem_pesq_grad_f32``, rows at 16 kHz),
+        float64 in CPU mode (any rate ``scores`` takes).  The clean rows are constants; a row under 20
+        frames (NaN), with a non-finite score or sample, or on the engine's range path gets a zero gradient."""
+        return self._differentiable(clean_speech, denoised_speech, sample_rate, lengths)[0]
+
+    def loss(self, clean_speech: torch.Tensor, denoised_speech: torch.Tensor, sample_rate: int | None = None,
+             lengths=None, key: str = "PESQ") -> torch.Tensor:
+        """A scalar that carries the gradient with respect to ``denoised_speech``, over the rows that have
+        at least 20 frames: ``key="PESQ"`` -mean MOS; ``key="distance"`` +mean of 0.1 d_sym + 0.0309 d_asym,
+        the quantity under the MOS mapping's sigmoid, which does not saturate at either end of the scale.
+        With no such row: a zero with a zero gradient."""
+        if key not in self.KEYS_LOSS:
+            raise ValueError(f"key must be one of {list(self.KEYS_LOSS)}, not {key!r}")
+        mos, sym, asym, scored = self._differentiable(clean_speech, denoised_speech, sample_rate, lengths)
+        score = -mos if key == "PESQ" else 0.1 * sym + 0.0309 * asym
+        scored = scored.to(score.device)
+        count = int(scored.sum())
+        total = torch.where(scored, score, torch.zeros((), dtype=score.dtype, device=score.device)).sum()
+        if count == 0:
+            # (an empty sum of the estimate: a zero on the graph, whose gradient is zero)
+            return total * 0 + torch.as_tensor(denoised_speech).reshape(-1)[:0].sum().to(total)
+        return total / count
 
     def p862_scores(self, clean_speech: torch.Tensor, noisy_speech: torch.Tensor, lengths=None):
         """The ``time_align="p862"`` scores of 16 kHz rows (extension, not in the reference,

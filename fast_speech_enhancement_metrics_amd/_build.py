@@ -20,7 +20,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 STAMP_LIB = os.path.join(LIBDIR, "libfsem_stamps.so")  # diagnostic build (tools/stamps.py)
-SOURCES = ["pesq.hip", "pesq_back.hip", "stoi.hip", "stoi_grad.hip", "resample.hip", "align.hip", "sdr.hip",
+SOURCES = ["pesq.hip", "pesq_back.hip", "pesq_grad.hip", "stoi.hip", "stoi_grad.hip", "resample.hip", "align.hip", "sdr.hip",
            "spectral.hip", "srmr.hip", "bsseval.hip", "pitsdr.hip", "runtime.hip"]
 # per-source code-generation flags: the STOI kernels and the resamplers are scheduled for ILP
 # (gfx950's max-ilp machine scheduler: joint call 7.167 vs 7.198 ms, profiles/r4_sc/; config 5
@@ -34,7 +34,8 @@ _ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # wave ~4 cycles: SQ_ACTIVE_INST_SCA / SQ_INSTS_SALU = 1 quad-cycle), and the packed forms that
 # pay (FFT butterflies, pass 1's functionals, pass 2's cascade) are written out explicitly.
 # Joint front end 4.478 -> 4.392 ms per 4096-row launch, profiles/r5_pk/.  The back end
-# (pesq_back.hip) keeps it: its 49-band loops pack into fewer instructions with it.
+# (pesq_back.hip) keeps it: its 49-band loops pack into fewer instructions with it, and so does
+# the backward (pesq_grad.hip), whose row kernel has the same band loops.
 SOURCE_FLAGS = {"pesq.hip": ["-fno-slp-vectorize"], "stoi.hip": _ILP, "resample.hip": _ILP}
 HEADERS = ["fsem_build_marker.h", "fsem_common.h", "fsem_corr512.h", "fsem_fft.h", "fsem_internal.h", "fsem_lpc.h",
            "fsem_pesq.h", "fsem_resample.h", "fsem_select.h", "fsem_speech_frames.h", "fsem_stoi.h", "fsem_tables.inc",
@@ -59,8 +60,8 @@ class Library(NamedTuple):
 # after the core has a library of its own (the four metric libraries' entry sets are pinned name by
 # name, and so are the core's workspace queries and the entries that take a workspace: the core
 # still takes entries without one, as fsem_spectral_* in spectral.hip, fsem_srmr_* in srmr.hip,
-# fsem_bsseval_* in bsseval.hip, fsem_pitsdr_* in pitsdr.hip and fsem_stoi_state_* / fsem_stoi_grad_* in
-# stoi_grad.hip); they
+# fsem_bsseval_* in bsseval.hip, fsem_pitsdr_* in pitsdr.hip, fsem_stoi_state_* / fsem_stoi_grad_* in
+# stoi_grad.hip and fsem_pesq_state_* / fsem_pesq_grad_* in pesq_grad.hip); they
 # use fsem_common.h (the Arena, the launch helpers) and link alone, except Composite's, whose
 # PESQ stage calls into libfsem.so.  A further library is one more entry here, a binding table in
 # _native, its header and its source.

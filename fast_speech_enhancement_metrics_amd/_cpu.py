@@ -122,7 +122,7 @@ def frame_disturbances(ec: torch.Tensor, en: torch.Tensor):
     lc, ln = loudness(ec), loudness(en)
     d = ln - lc
     d = d.sign() * (d.abs() - 0.25 * torch.minimum(lc, ln)).clamp(min=0)
-    sym = (math.sqrt(_TW) * torch.sqrt(((wb * d)[:, :, 1:] ** 2).sum(2))).clamp(min=1e-20)
+    sym = (math.sqrt(_TW) * _Sqrt0.apply(((wb * d)[:, :, 1:] ** 2).sum(2))).clamp(min=1e-20)  # (same values)
     a = ((en + 50.0) / (ec + 50.0)) ** 1.2
     a = torch.where(a < 3.0, torch.zeros_like(a), a).clamp(max=12.0)
     asym = (wb * d * a)[:, :, 1:].abs().sum(2).clamp(min=1e-20)
@@ -158,6 +158,59 @@ def pesq_distances(clean: torch.Tensor, noisy: torch.Tensor):
 def pesq(clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
     """[B, L] 16 kHz float32 -> MOS [B] float64."""
     return mos_of(*pesq_distances(clean, noisy))
+
+
+class _BandPass(torch.autograd.Function):
+    """The level band-pass of ``bandpass_power`` on [N, L] float64 rows from zero state; its adjoint is the
+    same cascade run backwards in time from zero state at the row's end."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return torch.from_numpy(sosfilt(_BP_SOS, x.detach().numpy(), axis=1))
+
+    @staticmethod
+    def backward(ctx, g):
+        return torch.from_numpy(sosfilt(_BP_SOS, g.numpy()[:, ::-1], axis=1)[:, ::-1].copy())
+
+
+class _PreEmphasis(torch.autograd.Function):
+    """The pre-emphasis IIR of ``pre_emphasize`` (without the taper) and its adjoint, as _BandPass."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return torch.from_numpy(lfilter(_PRE_B, _PRE_A, x.detach().numpy(), axis=1))
+
+    @staticmethod
+    def backward(ctx, g):
+        return torch.from_numpy(lfilter(_PRE_B, _PRE_A, g.numpy()[:, ::-1], axis=1)[:, ::-1].copy())
+
+
+def pesq_differentiable(clean: torch.Tensor, noisy: torch.Tensor):
+    """[B, L] 16 kHz -> (MOS, symmetric distance, asymmetric distance) [B] float64: ``pesq`` as a function
+    of the denoised rows under torch's autograd (include/fsem.h, "PESQ with gradients").  The clean rows
+    are constants; every decision (audible and silent masks, dead zone, a < 3) is a constant, every clamp
+    passes the gradient inside its range, a zero symmetric disturbance takes the subgradient 0."""
+    B, L = clean.shape
+    F = pesq_frames(L)
+    if F < 20:
+        raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(F, 0)} but size is 20")
+    bc = bark_of_rows(clean)
+    y = noisy.to("cpu", torch.float64)
+    u = _BandPass.apply(y)
+    y = y * level_scale((u * u).sum(1), L).sqrt()[:, None]
+    w = torch.ones(L, dtype=torch.float64)
+    w[:15] *= _TAPER
+    w[-15:] *= _TAPER.flip(0)
+    y = _PreEmphasis.apply(y * w)
+    if L % 256:
+        y = torch.nn.functional.pad(y, (0, L % 256))
+    z = torch.fft.rfft(y.unfold(1, 512, 256) * torch.hann_window(512, dtype=torch.float64), dim=2)
+    keep = torch.ones(257, dtype=torch.float64)
+    keep[0] = 0.0
+    ec, en = equalize(bc, bark_bands((z.real.square() + z.imag.square()) * keep))
+    sym, asym = frame_disturbances(ec, en)
+    sd, ad = overlapping_sums(sym), overlapping_sums(asym)
+    return mos_of(sd, ad), sd, ad
 
 
 # ----------------------------------------------------------------------------- STOI

@@ -107,6 +107,9 @@ SIGNATURES = {
     "fsem_stoi_state_floats": (_c_i64, [_c_i64, _c_i64, _c_i32]),
     "fsem_stoi_state_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp]),
     "fsem_stoi_grad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "fsem_pesq_state_floats": (_c_i64, [_c_i64, _c_i64]),
+    "fsem_pesq_state_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp]),
+    "fsem_pesq_grad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

@@ -43,6 +43,28 @@ __host__ __device__ inline Geometry geometry(int64_t L) {
   return g;
 }
 
+// Device functions the forward (pesq.hip, pesq_back.hip) and the backward (pesq_grad.hip) share.
+// PESQ.py:90,108-109: first 15 samples x (t+1)/16, last 15 samples x (L-t)/16, else 1:
+// w(t) = sat((t+1)/16) * sat((L-t)/16), exact in float32 for t, L < 2^24.
+__device__ __forceinline__ float taper_w(float tf, float Lf) {
+  return __saturatef((tf + 1.f) * 0.0625f) * __saturatef((Lf - tf) * 0.0625f);
+}
+
+// x^e for x > 0 (every call site: x >= 0.5 or a ratio of positive terms) via the hardware
+// v_log_f32 / v_exp_f32 (~1 ulp each); the reference evaluates these in float64, the
+// difference is ~1e-7 relative, far inside the +-0.01 MOS tolerance.
+__device__ __forceinline__ float pow_pos(float x, float e) {
+  return __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x));
+}
+
+__device__ __forceinline__ float loud(float p, int b) {
+  // loudness.py:64-65: (2T)^e ((0.5 + 0.5 P/T)^e - 1), 0 where P <= T; times Sl (folded).
+  // 0.5 P/T as P * (0.5/T) (one rounding instead of a correctly rounded division: <=1 ulp)
+  // branch-free (p >= 0: the pow argument is >= 0.5 either way)
+  const float v = kLoud2TE[b] * (pow_pos(fmaf(p, kHalfInvThresh[b], 0.5f), kLoudExp[b]) - 1.f);
+  return (p > kThresh[b]) ? v : 0.f;
+}
+
 // Workspace layouts (Arena, fsem_common.h).
 // Front end: per-segment power partials [2B, nseg, 4], then the range bookkeeping: the segments'
 // range shifts [2B, nseg] (pesq_front's pexp, read by the back end), worklist count, item queue,

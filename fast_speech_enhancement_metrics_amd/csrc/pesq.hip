@@ -97,11 +97,7 @@ static_assert(64 * SCAN_LD <= SCAN_A_WAVE && SCAN_B0 + PT * SCAN_LD <= XBUF && (
 static_assert(SPEC_LD * (NF - 1) + 256 <= TILE, "parked spectra stay in the tile");
 static_assert(TILE % (4 * PT) == 0, "tile load split");
 
-// PESQ.py:90,108-109: first 15 samples x (t+1)/16, last 15 samples x (L-t)/16, else 1:
-// w(t) = sat((t+1)/16) * sat((L-t)/16), exact in float32 for t, L < 2^24.
-__device__ __forceinline__ float taper_w(float tf, float Lf) {
-  return __saturatef((tf + 1.f) * 0.0625f) * __saturatef((Lf - tf) * 0.0625f);
-}
+// (taper_w: fsem_pesq.h, shared with the backward, pesq_grad.hip)
 
 // Range of a tile: float32 squares and |X|^2 of the band-pass / pre-emphasis outputs stay
 // finite and normal for tile scales within [2^-40, 2^40] (the scale: the peak magnitude of the

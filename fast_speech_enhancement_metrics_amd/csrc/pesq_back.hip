@@ -12,21 +12,7 @@ namespace fsem {
 namespace pesq {
 
 // ------------------------------------------------------------------------------ back end
-// x^e for x > 0 (every call site: x >= 0.5 or a ratio of positive terms) via the hardware
-// v_log_f32 / v_exp_f32 (~1 ulp each); the reference evaluates these in float64, the
-// difference is ~1e-7 relative, far inside the +-0.01 MOS tolerance.
-__device__ __forceinline__ float pow_pos(float x, float e) {
-  return __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x));
-}
-
-__device__ __forceinline__ float loud(float p, int b) {
-  // loudness.py:64-65: (2T)^e ((0.5 + 0.5 P/T)^e - 1), 0 where P <= T; times Sl (folded).
-  // 0.5 P/T as P * (0.5/T) (one rounding instead of a correctly rounded division: <=1 ulp)
-  // branch-free (p >= 0: the pow argument is >= 0.5 either way)
-  const float v = kLoud2TE[b] * (pow_pos(fmaf(p, kHalfInvThresh[b], 0.5f), kLoudExp[b]) - 1.f);
-  return (p > kThresh[b]) ? v : 0.f;
-}
-
+// (pow_pos and loud: fsem_pesq.h, shared with the backward, pesq_grad.hip)
 // BW waves per utterance, lane = frame: each load brings one band of 64 consecutive frames
 // (band-major rows, bark_ld), straight into registers -- no LDS staging, so occupancy is set
 // by VGPRs alone (the frame's 49 clean and 49 denoised band values stay in registers per chunk).

@@ -673,6 +673,60 @@ int fsem_stoi_grad_f32(const float *deg, int64_t batch, int64_t length, int64_t 
                        int32_t sample_rate, float *state, const float *g_stoi, const float *g_estoi,
                        float *grad, int64_t grad_ld, void *stream);
 
+/* ---------------------------------------------------------------- PESQ with gradients
+ * The wideband PESQ of fsem_pesq_wb_f32 as a function to train against: the scores, and the gradient of
+ *   L = sum_b (g_mos[b] MOS_b + g_sym[b] d_sym_b + g_asym[b] d_asym_b)
+ * with respect to the denoised rows at 16 kHz.  (Joined at ABI 11 without a bump, as above.)
+ * The function differentiated is "PESQ" above taken as a function of the denoised row x of length L:
+ * u = BP(x) from zero state and P = sum u^2; sigma = 1e7 (L + 5120) 1.04684 / P; the row times sqrt(sigma),
+ * times the 15-sample edge tapers, through the pre-emphasis IIR, padded by L % 256; Hann-512 frames at hop
+ * 256, |rFFT|^2 with bin 0 zeroed and bin 256 unused; the Bark contraction; then the band and frame
+ * equalisation, the loudness, the dead zone, both disturbances, the frame weighting, the L6 / L2 pooling and
+ * the MOS mapping.  The equalisation of ranges cancels exactly, so the scores do not depend on the scale of x
+ * and <grad, x> = 0.
+ *  - Clean rows are constants: no gradient with respect to ref.
+ *  - The decisions are constants of the function: the audible masks (> thr, > 100 thr), the silent-frame
+ *    mask, p <= thr in the loudness, the dead zone's clamp at 0 and its sign, a < 3 -> 0.
+ *  - Every clamp passes the gradient inside its range and 0 outside: the band ratio 0.01 .. 100, the frame
+ *    ratio 3e-4 .. 5, a <= 12, the floor 1e-20 and the cap 45.
+ *  - The symmetric disturbance sqrt(sum (w d)^2) takes the subgradient 0 where the sum is 0 (every band in
+ *    the dead zone), and so does any root or power whose argument is 0; |.| has derivative 0 at 0.  The
+ *    pooling runs in double, as the forward's.
+ *  - A gradient row of exact zeros goes to: a row with fewer than 20 frames; a row whose score is not
+ *    finite (zero band-pass power); a row with a non-finite sample among its lengths[b] samples; a row
+ *    with a tile the forward's range path had to rescale (peaks outside 2^+-40).  No other row is touched,
+ *    and the scores of these rows stay what fsem_pesq_wb_f32 gives.
+ *  - With lengths, grad[b, lengths[b] .. length) is zero and row b's gradient is that of the unpadded row,
+ *    with its own taper position and its own L % 256 padding.
+ *  - A row's gradient does not depend on the batch it is in, and two calls give the same bits: every
+ *    sum is a gather or a store-then-sum in a fixed order; no atomics, no hidden allocation.
+ *
+ *   state    : [fsem_pesq_state_floats(batch, length)] float32, owned by the caller, 256-byte aligned.  Its
+ *              head is the workspace of fsem_pesq_wb_f32, laid out as that entry lays it out (the power
+ *              partials, the range shifts, flags and worklist, both signals' unscaled Bark bands
+ *              [2 batch, 49, ceil32(frames)], the back end's scratch), which fsem_pesq_state_f32 leaves filled;
+ *              its tail is the backward's scratch: per row 6 frame rows and one of doubles, the band
+ *              gradients [49, ceil32(frames)], a coefficient and a flag, and two rows of ceil256(length)
+ *              samples (the pre-emphasised row and the gradient with respect to it): 1.69 MB per 10 s
+ *              row, 0.26 MB of it the forward's.
+ *   fsem_pesq_state_f32 : mos [batch] bitwise that of fsem_pesq_wb_f32 on the same batch (the same kernels
+ *              on the state's head); dist, NULL or [2, batch], bitwise that of fsem_pesq_wb_frames_f32.
+ *              FSEM_ESHORT as there.
+ *   fsem_pesq_grad_f32  : reads the state fsem_pesq_state_f32 left for the same deg, batch, length, ld and
+ *              lengths, writes the tail, and writes every element of grad[b, 0 .. length) (row b at
+ *              grad + b grad_ld).  It may be called again on the same state.
+ *   g_mos, g_sym, g_asym : [batch] float32 device arrays; g_sym and g_asym may be NULL (zeros).
+ * FSEM_EINVAL before any launch for null pointers (lengths, dist, g_sym and g_asym may be NULL), batch < 0,
+ * length <= 0, length > 2^29, ld < length, grad_ld < length (fsem_pesq_state_floats returns 0 for any of
+ * these).  batch == 0 is FSEM_OK with nothing launched.
+ */
+int64_t fsem_pesq_state_floats(int64_t batch, int64_t length);  /* 0 for refused arguments */
+int fsem_pesq_state_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                        const int32_t *lengths, float *mos, float *dist, float *state, void *stream);
+int fsem_pesq_grad_f32(const float *deg, int64_t batch, int64_t length, int64_t ld, const int32_t *lengths,
+                       float *state, const float *g_mos, const float *g_sym, const float *g_asym,
+                       float *grad, int64_t grad_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,263 @@
+"""PESQ with gradients on the HIP engine (csrc/pesq_grad.hip) against the float64 reference of
+tests/pesq_grad_cases.py: the forward bitwise against ``PESQ.scores``, the gradient of the MOS and of both
+distances on every case, the conventions (rows without a gradient and their neighbours, ragged rows),
+reproducibility, batch independence, exact scaling by powers of two, <g, x> = 0, row layouts, ``loss`` with both
+keys and one direct call of the C entries.
+
+The gradient's bar is ``gc.bar()``: 32 x the largest error of the float32 torch restatement against the same
+reference over the main, short and long sets.  The error of a row is max|g - g_ref| / max|g_ref|."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from fast_speech_enhancement_metrics_amd import PESQ, _native
+
+from . import pesq_grad_cases as gc
+
+pytestmark = pytest.mark.gpu
+NAMES = ["main", "short", "long", "odd", "zero", "bad"]
+ATOL_SCORE = 5e-3   # MOS against float64: the bar the smoke run holds the forward to (the subject here is the bitwise check)
+
+
+def _bits(t):
+    return t.detach().cpu().numpy().view(np.uint32)
+
+
+def engine(c, d, lengths=None, g=None):
+    """(mos, sym, asym, grad) of host rows on the engine; grad for incoming g = (g_mos, g_sym, g_asym) [B]."""
+    m = PESQ(16000, use_gpu=True)
+    est = d.cuda().requires_grad_(True)
+    mos, sym, asym, _ = m._differentiable(c.cuda(), est, 16000, lengths)
+    assert mos.is_cuda and mos.dtype == torch.float32 and mos.shape == sym.shape == asym.shape == (c.shape[0],)
+    if g is None:
+        return mos.detach(), sym.detach(), asym.detach(), None
+    # (a NaN score times a zero incoming gradient would be NaN in a sum: the rows' gradients come from the
+    # incoming gradients alone)
+    torch.autograd.backward([mos, sym, asym], [v.cuda() for v in g])
+    assert est.grad.shape == d.shape and est.grad.dtype == torch.float32
+    return mos.detach(), sym.detach(), asym.detach(), est.grad
+
+
+def upstream(B, u):
+    return tuple(torch.full((B,), float(v)) for v in u)
+
+
+@functools.lru_cache(maxsize=None)
+def engine_set(name, u):
+    c, d = gc.rows(name)
+    g = upstream(c.shape[0], u)
+    return engine(c, d, g=g) + (g,)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_forward_is_scores_bitwise(name):
+    c, d = gc.rows(name)
+    mos, sym, asym, _, _ = engine_set(name, gc.UPSTREAMS[0])
+    m = PESQ(16000, use_gpu=True)
+    s0 = m.scores(c.cuda(), d.cuda().requires_grad_(True))
+    assert s0.grad_fn is None and not s0.requires_grad
+    np.testing.assert_array_equal(_bits(mos), _bits(s0))
+    np.testing.assert_array_equal(_bits(m.differentiable_scores(c.cuda(), d.cuda())), _bits(s0))
+    want = gc.expected(name)["scores"]
+    got = torch.stack([mos, sym, asym], 1).cpu().numpy()
+    live = np.isfinite(want[:, 0])
+    assert np.isnan(got[~live, 0]).all()
+    np.testing.assert_allclose(got[live, 0], want[live, 0], rtol=0, atol=ATOL_SCORE)
+    np.testing.assert_allclose(got[live, 1:], want[live, 1:], rtol=1e-3, atol=0)
+
+
+@pytest.mark.parametrize("u", gc.UPSTREAMS, ids=["mos", "sym", "asym"])
+@pytest.mark.parametrize("name", NAMES)
+def test_gradient_against_the_reference(name, u):
+    want = gc.expected(name)
+    mos, _, _, grad, g = engine_set(name, u)
+    grad = grad.cpu().numpy()
+    err = gc.row_errors(grad, gc.combine(want, *[v.numpy() for v in g]))
+    print(f"{name} {u}: row errors {err}, bar {gc.bar():.3e}")
+    assert np.isfinite(grad).all() and err.max() <= gc.bar()
+    for b, ok in enumerate(gc.scored(name)):
+        if not ok:   # a row without a finite score: exact zeros
+            assert np.isnan(float(mos[b])) and (grad[b] == 0).all()
+    if name in ("zero", "bad"):   # the neighbours equal the same rows computed alone
+        c, d = gc.rows(name)
+        for b in (0, 2):
+            alone = engine(c[b:b + 1], d[b:b + 1], g=tuple(v[b:b + 1] for v in g))[3]
+            np.testing.assert_array_equal(_bits(alone[0]), _bits(torch.from_numpy(grad[b])))
+
+
+def test_an_infinite_sample_zeroes_its_row_only():
+    c, d = gc.rows("main")
+    _, _, _, base, g = engine_set("main", gc.UPSTREAMS[0])
+    bad = d.clone()
+    bad[1, 5000] = float("inf")
+    grad = engine(c, bad, g=g)[3]
+    assert (grad[1] == 0).all()
+    np.testing.assert_array_equal(_bits(grad[[0, 2, 3]]), _bits(base[[0, 2, 3]]))
+
+
+def test_ragged_rows():
+    c, d = gc.rows("main")
+    lens = gc.RAGGED_LENGTHS
+    want = gc.expected("main", tuple(lens))
+    for u in gc.UPSTREAMS:
+        g = upstream(4, u)
+        mos, _, _, grad = engine(c, d, lengths=lens, g=g)
+        err = gc.row_errors(grad.cpu().numpy(), gc.combine(want, *[v.numpy() for v in g]))
+        print(f"ragged {u}: row errors {err}, bar {gc.bar():.3e}")
+        assert err.max() <= gc.bar()
+        for b, nb in enumerate(lens):
+            assert (grad[b, nb:] == 0).all()
+        assert torch.isnan(mos[3]) and (grad[3] == 0).all()
+        # (row 1's asymmetric frames all sit at the cap 45, outside the clamp: that gradient alone is zero)
+        assert float(grad[1].abs().max()) > 0 or u == gc.UPSTREAMS[2]
+    # the unpadded row scored alone gives the same bits; the padding is never looked at
+    g = upstream(4, gc.UPSTREAMS[0])
+    mos, _, _, grad = engine(c, d, lengths=lens, g=g)
+    for b in (1, 2):
+        nb = lens[b]
+        pad = (-nb) % 4
+        m1, _, _, g1 = engine(c[b:b + 1, :nb + pad], d[b:b + 1, :nb + pad], lengths=[nb], g=tuple(v[:1] for v in g))
+        np.testing.assert_array_equal(_bits(m1), _bits(mos[b:b + 1]))
+        np.testing.assert_array_equal(_bits(g1[0, :nb]), _bits(grad[b, :nb]))
+    c2, d2 = c.clone(), d.clone()
+    c2[1, lens[1] + 3:], d2[1, lens[1] + 3:] = float("nan"), float("inf")   # (past ceil4 of the row's length)
+    np.testing.assert_array_equal(_bits(engine(c2, d2, lengths=lens, g=g)[3]), _bits(grad))
+
+
+def test_reproducible_and_batch_independent():
+    c, d = gc.rows("main")
+    _, _, _, base, g = engine_set("main", gc.UPSTREAMS[0])
+    np.testing.assert_array_equal(_bits(engine(c, d, g=g)[3]), _bits(base))
+    for b in range(4):
+        alone = engine(c[b:b + 1], d[b:b + 1], g=tuple(v[b:b + 1] for v in g))[3]
+        np.testing.assert_array_equal(_bits(alone[0]), _bits(base[b]))
+    # the long row alone and as row 1 of a batch of two
+    c, d = gc.rows("long")
+    _, _, _, base, g = engine_set("long", gc.UPSTREAMS[0])
+    two = engine(torch.cat([c, c]), torch.cat([d * 0.5, d]), g=tuple(v.repeat(2) for v in g))[3]
+    np.testing.assert_array_equal(_bits(two[1]), _bits(base[0]))
+
+
+def test_scale_invariance():
+    c, d = gc.rows("main")
+    mos, _, _, base, g = engine_set("main", gc.UPSTREAMS[0])
+    for k in (3, -3):
+        m2, _, _, grad = engine(c, d * 2.0 ** k, g=g)
+        np.testing.assert_array_equal(_bits(m2), _bits(mos))
+        np.testing.assert_array_equal(_bits(grad * 2.0 ** k), _bits(base))
+    # <g, x> = 0: the score does not depend on the scale of x
+    for name in ("main", "short", "long"):
+        c, d = gc.rows(name)
+        grad = engine_set(name, gc.UPSTREAMS[0])[3].cpu().double()
+        dot = (grad * d.double()).sum(1).abs()
+        bound = gc.bar() * grad.abs().amax(1) * d.double().abs().sum(1)
+        print(f"{name}: |<g, x>| {dot.tolist()}, bound {bound.tolist()}")
+        assert bool((dot <= bound).all())
+
+
+def test_row_layouts():
+    c, d = gc.rows("main")
+    _, _, _, base, g = engine_set("main", gc.UPSTREAMS[0])
+    m = PESQ(16000, use_gpu=True)
+    wide, cwide = torch.zeros(4, 16000 + 36).cuda(), torch.zeros(4, 16000 + 36).cuda()
+    wide[:, 12:16012], cwide[:, 12:16012] = d.cuda(), c.cuda()
+    est = wide.requires_grad_(True)
+    mos = m.differentiable_scores(cwide[:, 12:16012], est[:, 12:16012])   # slices: the engine reads them in place
+    mos.backward(g[0].cuda())
+    np.testing.assert_array_equal(_bits(est.grad[:, 12:16012]), _bits(base))
+    assert (est.grad[:, :12] == 0).all() and (est.grad[:, 16012:] == 0).all()
+    # a non-contiguous estimate (every other column) comes back in the caller's shape
+    inter = torch.zeros(4, 32000).cuda()
+    inter[:, ::2] = d.cuda()
+    est = inter.requires_grad_(True)
+    m.differentiable_scores(c.cuda(), est[:, ::2]).backward(g[0].cuda())
+    assert est.grad.shape == (4, 32000) and (est.grad[:, 1::2] == 0).all()
+    np.testing.assert_array_equal(_bits(est.grad[:, ::2]), _bits(base))
+    # an odd length against its zero-padded copy with lengths
+    c, d = gc.rows("odd")
+    _, _, _, odd, g = engine_set("odd", gc.UPSTREAMS[0])
+    assert odd.shape == (4, gc.ODD_LENGTH)
+    pad = torch.nn.functional.pad
+    padded = engine(pad(c, (0, 3)), pad(d, (0, 3)), lengths=[gc.ODD_LENGTH] * 4, g=g)[3]
+    np.testing.assert_array_equal(_bits(padded[:, :gc.ODD_LENGTH]), _bits(odd))
+    # half precision estimates: cast to float32, the gradient back in their dtype
+    half = d.cuda().to(torch.bfloat16).requires_grad_(True)
+    m.loss(c.cuda(), half).backward()
+    assert half.grad.dtype == torch.bfloat16 and bool(torch.isfinite(half.grad.float()).all())
+
+
+def test_loss_and_a_retained_graph():
+    c, d = gc.rows("main")
+    lens = gc.RAGGED_LENGTHS
+    want = gc.expected("main", tuple(lens))
+    m = PESQ(16000, use_gpu=True)
+    est = d.cuda().requires_grad_(True)
+    sc = want["scores"][:3]
+    for key, value, ref in (("PESQ", -sc[:, 0].mean(), -want["gm"] / 3),
+                            ("distance", (0.1 * sc[:, 1] + 0.0309 * sc[:, 2]).mean(),
+                             (0.1 * want["gs"] + 0.0309 * want["ga"]) / 3)):
+        est.grad = None
+        loss = m.loss(c.cuda(), est, lengths=lens, key=key)
+        assert loss.dtype == torch.float32 and loss.dim() == 0
+        assert abs(float(loss.detach()) - value) <= 1e-4 * max(1.0, abs(value))
+        loss.backward(retain_graph=True)
+        first = est.grad.clone()
+        err = gc.row_errors(first.cpu().numpy(), ref)
+        print(f"loss {key}: row errors {err}, bar {gc.bar():.3e}")
+        assert err.max() <= gc.bar() and (first[3] == 0).all()
+        est.grad = None
+        loss.backward()   # a second backward through the retained graph: the same bits
+        np.testing.assert_array_equal(_bits(est.grad), _bits(first))
+    short = d[:, :3000].cuda().requires_grad_(True)
+    loss = m.loss(c[:, :3000].cuda(), short, lengths=[3000] * 4)
+    assert float(loss.detach()) == 0.0
+    loss.backward()
+    assert (short.grad == 0).all()
+    with pytest.raises(NotImplementedError, match="constants"):
+        m.loss(c.cuda().requires_grad_(True), est)
+    with pytest.raises(NotImplementedError, match="16 kHz"):
+        PESQ(8000, use_gpu=True).loss(c.cuda(), est, sample_rate=8000)
+    fan = PESQ(16000, use_gpu=True)
+    fan._fanout = object()   # (stands in for a metric built with devices=)
+    with pytest.raises(NotImplementedError, match="devices"):
+        fan.loss(c.cuda(), est)
+
+
+def test_c_entries_directly():
+    lib = _native.load()
+    c, d = gc.rows("short")
+    B, L = c.shape
+    ld, grad_ld = L + 8, L + 12
+    pad = torch.nn.functional.pad
+    cd, nd = pad(c, (0, 8)).cuda(), pad(d, (0, 8)).cuda()
+    mos = torch.empty(B, device="cuda")
+    dist = torch.empty(2, B, device="cuda")
+    state = torch.empty(lib.fsem_pesq_state_floats(B, L), device="cuda")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    st = _native.stream_handle(cd.device)
+    assert lib.fsem_pesq_state_f32(p(cd), p(nd), B, L, ld, None, p(mos), p(dist), p(state), st) == _native.FSEM_OK
+    m0, s0, a0, base, g = engine_set("short", gc.UPSTREAMS[0])
+    np.testing.assert_array_equal(_bits(mos), _bits(m0))
+    np.testing.assert_array_equal(_bits(dist), _bits(torch.stack([s0, a0])))
+    mos2 = torch.empty(B, device="cuda")   # without the distances: the scoring instance, the same bits
+    assert lib.fsem_pesq_state_f32(p(cd), p(nd), B, L, ld, None, p(mos2), None, p(state), st) == _native.FSEM_OK
+    np.testing.assert_array_equal(_bits(mos2), _bits(m0))
+    grad = torch.full((B, grad_ld), 7.0, device="cuda")
+    gm = g[0].cuda()
+    for _ in range(2):   # (the state may be read again)
+        assert lib.fsem_pesq_grad_f32(p(nd), B, L, ld, None, p(state), p(gm), None, None, p(grad), grad_ld, st) == \
+            _native.FSEM_OK
+        np.testing.assert_array_equal(_bits(grad[:, :L]), _bits(base))
+        assert (grad[:, L:] == 7.0).all()   # the padding columns are not written
+    # refusals come back before any launch
+    assert lib.fsem_pesq_grad_f32(p(nd), B, L, ld, None, p(state), p(gm), None, None, p(grad), L - 1, st) == \
+        _native.FSEM_EINVAL
+    for args in ((None, p(state), p(gm), p(grad)), (p(nd), None, p(gm), p(grad)), (p(nd), p(state), None, p(grad)),
+                 (p(nd), p(state), p(gm), None)):
+        assert lib.fsem_pesq_grad_f32(args[0], B, L, ld, None, args[1], args[2], None, None, args[3], grad_ld, st) == \
+            _native.FSEM_EINVAL
+    assert (grad[:, L:] == 7.0).all()
+    np.testing.assert_array_equal(_bits(grad[:, :L]), _bits(base))
