@@ -125,7 +125,7 @@ class BSSEval(BaseMetric):
         norms = torch.empty(B, S + E, dtype=torch.float32, device=dev)
         corr = torch.empty(B, lib.fsem_bsseval_corr_doubles(S, E, L), dtype=torch.float64, device=dev)
         rc = lib.fsem_bsseval_f32(src.data_ptr(), est.data_ptr(), B, S, E, L, ld,
-                                  lens.data_ptr() if lens is not None else None, norms.data_ptr(), corr.data_ptr(),
+                                  _native.ptr(lens), norms.data_ptr(), corr.data_ptr(),
                                   coh.data_ptr(), coh_all.data_ptr(), _native.stream_handle(dev))
         _native.check(rc, "BSSEval")
         return coh, coh_all, norms, corr
@@ -142,8 +142,8 @@ class BSSEval(BaseMetric):
         sdm, sim = (torch.empty(B, S, E, dtype=torch.float32, device=dev) if matrices else None for _ in range(2))
         rc = _native.load().fsem_bsseval_scores_f32(
             coh.data_ptr(), coh_all.data_ptr(), B, S, E, _cpu.BSSEVAL_CRITERIA[criterion], sdr.data_ptr(),
-            sir.data_ptr(), sar.data_ptr(), perm.data_ptr(), sdm.data_ptr() if matrices else None,
-            sim.data_ptr() if matrices else None, _native.stream_handle(dev))
+            sir.data_ptr(), sar.data_ptr(), perm.data_ptr(), _native.ptr(sdm), _native.ptr(sim),
+            _native.stream_handle(dev))
         _native.check(rc, "BSSEval scores")
         return sdr, sir, sar, perm, sdm, sim
 

@@ -74,7 +74,7 @@ class BSSSDR(BaseMetric):
         if B == 0:
             return out
         ws = _native.workspace(lib.fsem_bsssdr_workspace_bytes(B, L), clean.device)
-        lp = lens.data_ptr() if lens is not None else None
+        lp = _native.ptr(lens)
         if diag is None:
             rc = lib.fsem_bsssdr_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0), lp, out.data_ptr(),
                                      ws.data_ptr(), ws.numel(), _native.stream_handle(clean.device))

@@ -70,7 +70,7 @@ class Composite(BaseMetric):
             return tuple(out.fill_(float("nan")))
         ws = _native.workspace(lib.fsem_composite_workspace_bytes(B, L, sr), clean.device)
         rc = lib.fsem_composite_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                                    lens.data_ptr() if lens is not None else None, sr,
+                                    _native.ptr(lens), sr,
                                     *(out[k].data_ptr() for k in range(7)), ws.data_ptr(), ws.numel(),
                                     _native.stream_handle(clean.device))
         _native.check(rc, "Composite")

@@ -159,7 +159,7 @@ class DNSMOS(BaseMetric):
         lib = _native.load_dnsmos()
         blob = self.blob(rows.device)
         ws = _native.workspace(lib.fsem_dnsmos_workspace_bytes(B, L), rows.device)
-        rc = lib.fsem_dnsmos_f32(rows.data_ptr(), B, L, rows.stride(0), lens.data_ptr() if lens is not None else None,
+        rc = lib.fsem_dnsmos_f32(rows.data_ptr(), B, L, rows.stride(0), _native.ptr(lens),
                                  blob.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                  _native.stream_handle(rows.device))
         _native.check(rc, "DNSMOS")

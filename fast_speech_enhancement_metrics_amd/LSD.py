@@ -74,7 +74,7 @@ class LSD(BaseMetric):
             return out
         ws = _native.workspace(lib.fsem_lsd_workspace_bytes(B, L), clean.device)
         rc = lib.fsem_lsd_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                              lens.data_ptr() if lens is not None else None, out.data_ptr(), ws.data_ptr(),
+                              _native.ptr(lens), out.data_ptr(), ws.data_ptr(),
                               ws.numel(), _native.stream_handle(clean.device))
         _native.check(rc, "LSD")
         return out

@@ -16,7 +16,8 @@ import torch
 
 from . import _cpu, _native
 from .bark import BarkFilterBank
-from .base import BaseMetric, as_rows, check_row_rate, device_lengths, noisy_shape, resample_rows, same_device
+from .base import (BaseMetric, as_rows, check_row_rate, device_lengths, engine_rows, grad_buffer, grad_engine_rows,
+                   grad_operands, noisy_shape, pair_rows, resample_rows, same_device, scored_mean)
 from .loudness import Loudness
 from .spectrogram import Spectrogram
 
@@ -33,27 +34,29 @@ def _unit_rows(x: torch.Tensor, lengths=None) -> torch.Tensor:
     return x * torch.exp2(-ex).to(x.dtype)[:, None]  # a power of two: exact, as ldexp
 
 
+def _too_short(F: int) -> RuntimeError:
+    """The reference's unfold(1, size=20, step=10) fails on fewer than 20 frames (PESQ.py:169)."""
+    return RuntimeError(f"maximum size for tensor at dimension 1 is {max(F, 0)} but size is 20")
+
+
 def _wb_frames(lib, clean: torch.Tensor, noisy: torch.Tensor, lens):
     """(distances [2, B], per-frame disturbances [B, 2, F]) of 16 kHz rows on the GPU through the
     whole-metric entry (fsem_pesq_wb_frames_f32: its range handling, no host-side row scaling)."""
-    clean = as_rows(clean)
-    noisy = as_rows(noisy)
+    # (this path hands the entry rows that lie back to back: views with a longer row stride are copied)
+    clean, noisy = as_rows(clean).contiguous(), as_rows(noisy).contiguous()
     B, L = clean.shape
     F = lib.fsem_pesq_frames(L)
     if F < 20 and lens is None:
-        raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(F, 0)} but size is 20")
-    if clean.stride(0) != noisy.stride(0) or L % 4 or not (clean.is_contiguous() and noisy.is_contiguous()):
-        pad = (-L) % 4
-        clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-        noisy = torch.nn.functional.pad(noisy, (0, pad)).contiguous()
+        raise _too_short(F)
+    clean, noisy, L, lens = engine_rows(clean, noisy, lens)
     mos = torch.empty(B, dtype=torch.float32, device=clean.device)
     dist = torch.empty(2, B, dtype=torch.float32, device=clean.device)
     frames = torch.full((B, 2, F), float("nan"), device=clean.device)
     ws = _native.workspace(lib.fsem_pesq_workspace_bytes(B, L), clean.device)
     _native.check(lib.fsem_pesq_wb_frames_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                                              lens.data_ptr() if lens is not None else None, mos.data_ptr(),
-                                              dist.data_ptr(), frames.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              _native.stream_handle(clean.device)), "PESQ frames")
+                                              _native.ptr(lens), mos.data_ptr(), dist.data_ptr(), frames.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _native.stream_handle(clean.device)),
+                  "PESQ frames")
     return dist[0], frames
 
 
@@ -74,12 +77,10 @@ class _EngineScores(torch.autograd.Function):
         if B == 0:
             return mos, dist[0], dist[1]
         state = torch.empty(lib.fsem_pesq_state_floats(B, L), dtype=torch.float32, device=dev)  # (outlives the call)
-        rc = lib.fsem_pesq_state_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                                     lens.data_ptr() if lens is not None else None, mos.data_ptr(), dist.data_ptr(),
-                                     state.data_ptr(), _native.stream_handle(dev))
+        rc = lib.fsem_pesq_state_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0), _native.ptr(lens),
+                                     mos.data_ptr(), dist.data_ptr(), state.data_ptr(), _native.stream_handle(dev))
         if rc == _native.FSEM_ESHORT:
-            raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(lib.fsem_pesq_frames(L), 0)} "
-                               "but size is 20")
+            raise _too_short(lib.fsem_pesq_frames(L))
         _native.check(rc, "PESQ")
         ctx.state, ctx.noisy, ctx.lens = state, noisy, lens
         return mos, dist[0], dist[1]
@@ -87,17 +88,14 @@ class _EngineScores(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_mos, g_sym, g_asym):
-        B, L, width = ctx.shape
-        if ctx.state is None:
-            return torch.zeros(B, width, dtype=torch.float32, device=g_mos.device), None, None, None
-        grad = torch.empty(B, width, dtype=torch.float32, device=g_mos.device)  # (the entry writes [:, :L])
-        grad[:, L:] = 0
-        g = [v.to(torch.float32).contiguous() for v in (g_mos, g_sym, g_asym)]
-        lens = ctx.lens
+        B, L, _ = ctx.shape
+        grad, g = grad_buffer(ctx.shape, ctx.state is not None, (g_mos, g_sym, g_asym))
+        if g is None:
+            return grad, None, None, None
         rc = _native.load().fsem_pesq_grad_f32(
-            ctx.noisy.data_ptr(), B, L, ctx.noisy.stride(0), lens.data_ptr() if lens is not None else None,
-            ctx.state.data_ptr(), g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), grad.data_ptr(), grad.stride(0),
-            _native.stream_handle(g_mos.device))
+            ctx.noisy.data_ptr(), B, L, ctx.noisy.stride(0), _native.ptr(ctx.lens), ctx.state.data_ptr(),
+            g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), grad.data_ptr(), grad.stride(0),
+            _native.stream_handle(grad.device))
         _native.check(rc, "PESQ backward")
         return grad, None, None, None
 
@@ -283,26 +281,21 @@ class PESQ(BaseMetric):
         fsem_pesq_distances_f32); rows under 20 frames give NaN distances."""
         # each signal is level-aligned on its own (PESQ.py:92-102), so scaling a row by a power of
         # two changes nothing but the range: rows go in with peaks in [1, 2), as _front
-        same_device(as_rows(clean_speech), as_rows(noisy_speech))
-        clean = _unit_rows(as_rows(clean_speech), lengths)
-        noisy = _unit_rows(as_rows(noisy_speech), lengths)
+        clean, noisy = as_rows(clean_speech), as_rows(noisy_speech)
+        same_device(clean, noisy)
         lib = _native.load()
-        B, L = clean.shape
+        B = clean.shape[0]
+        clean, noisy, L, lens = engine_rows(_unit_rows(clean, lengths), _unit_rows(noisy, lengths), lengths)
         F = lib.fsem_pesq_frames(L)
-        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
         if F < 20 and lens is None:
-            raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(F, 0)} but size is 20")
-        if clean.stride(0) != noisy.stride(0) or L % 4:
-            pad = (-L) % 4
-            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-            noisy = torch.nn.functional.pad(noisy, (0, pad)).contiguous()
+            raise _too_short(F)
         fld = (F + 31) // 32 * 32
         bark = torch.empty(2 * B, 49, fld, device=clean.device)
         power = torch.empty(2 * B, device=clean.device)
         st = _native.stream_handle(clean.device)
         ws = _native.workspace(max(lib.fsem_pesq_front_workspace_bytes(B, L),
                                    lib.fsem_pesq_distances_workspace_bytes(B, L)), clean.device)
-        lp = lens.data_ptr() if lens is not None else None
+        lp = _native.ptr(lens)
         _native.check(lib.fsem_pesq_front_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0), lp,
                                               bark.data_ptr(), power.data_ptr(), ws.data_ptr(), ws.numel(), st),
                       "PESQ front")
@@ -353,12 +346,8 @@ class PESQ(BaseMetric):
         if sr != self.EXPECTED_SAMPLING_RATE:
             clean_speech, denoised_speech, lengths = resample_rows(clean_speech, denoised_speech, lengths, sr,
                                                                    self.EXPECTED_SAMPLING_RATE)
-        clean = as_rows(clean_speech)
-        noisy = as_rows(denoised_speech)
+        clean, noisy = pair_rows(clean_speech, denoised_speech)
         B, L = clean.shape
-        if noisy.shape != clean.shape:
-            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
-        same_device(clean, noisy)
         if getattr(self, "time_align", False) == "p862":
             mos, delays, _, _ = self.p862_scores(clean, noisy, lengths)
             return mos, delays
@@ -370,20 +359,13 @@ class PESQ(BaseMetric):
             if lengths is None:
                 return _cpu.rows_parallel(_cpu.pesq, clean, noisy), delays
             return _cpu.per_row(_cpu.pesq, clean, noisy, device_lengths(lengths, B, L, "cpu")), delays
+        clean, noisy, L, lens = engine_rows(clean, noisy, lengths)
         F = lib.fsem_pesq_frames(L)
-        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
         if F < 20 and lens is None:
-            # the reference's unfold(1, size=20, step=10) fails here (PESQ.py:169)
-            raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(F, 0)} but size is 20")
-        if clean.stride(0) != noisy.stride(0) or L % 4:
-            # rows must be readable up to ceil4(L) floats (include/fsem.h): pad odd lengths
-            pad = (-L) % 4
-            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-            noisy = torch.nn.functional.pad(noisy, (0, pad)).contiguous()
+            raise _too_short(F)
         mos = torch.empty(B, dtype=torch.float32, device=clean.device)
         ws = _native.workspace(lib.fsem_pesq_workspace_bytes(B, L), clean.device)
-        _native.check(lib.fsem_pesq_wb_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                                           lens.data_ptr() if lens is not None else None,
+        _native.check(lib.fsem_pesq_wb_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0), _native.ptr(lens),
                                            mos.data_ptr(), ws.data_ptr(), ws.numel(),
                                            _native.stream_handle(clean.device)), "PESQ")
         return mos, delays
@@ -404,36 +386,19 @@ class PESQ(BaseMetric):
                                       "differentiable): align the rows first (alignment.time_align) and use "
                                       "PESQ(time_align=False)")
         sr = check_row_rate(self, sample_rate)
-        clean, noisy = torch.as_tensor(clean_speech), torch.as_tensor(denoised_speech)
-        if clean.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("PESQ: the clean rows are constants; gradients with respect to `clean_speech` "
-                                      "are not supported (detach them)")
-        clean, noisy = torch.atleast_2d(clean.detach()), torch.atleast_2d(noisy)
-        if noisy.shape != clean.shape or clean.dim() != 2:
-            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
-        same_device(clean, noisy)
-        B, L = clean.shape
+        clean, noisy = grad_operands(self, clean_speech, denoised_speech)
         if not clean.is_cuda:
             return self._differentiable_cpu(clean, noisy, sr, lengths)
         if sr != self.EXPECTED_SAMPLING_RATE:
             raise NotImplementedError(f"PESQ: the engine's gradients take rows at 16 kHz, not {sr} Hz: resample the "
                                       "rows first with differentiable torch ops, or use PESQ(use_gpu=False)")
-        lib = _native.load()
-        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
-        if lib.fsem_pesq_frames(L) < 20 and lens is None:
-            raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(lib.fsem_pesq_frames(L), 0)} "
-                               "but size is 20")
-        clean, rows = as_rows(clean), noisy.to(torch.float32)  # (autograd casts the gradient back)
-        if rows.stride(-1) != 1 or rows.stride(0) < L:
-            rows = rows.contiguous()
-        if clean.stride(0) != rows.stride(0) or L % 4:
-            # rows must be readable up to ceil4(L) floats (include/fsem.h): pad odd lengths
-            pad = (-L) % 4
-            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-            rows = torch.nn.functional.pad(rows, (0, pad)).contiguous()
+        clean, rows, L, lens = grad_engine_rows(clean, noisy, lengths)
+        F = _native.load().fsem_pesq_frames(L)
+        if F < 20 and lens is None:
+            raise _too_short(F)
         mos, sym, asym = _EngineScores.apply(rows, clean, lens, L)
         if lens is None:
-            scored = torch.ones(B, dtype=torch.bool, device=clean.device)
+            scored = torch.ones(clean.shape[0], dtype=torch.bool, device=clean.device)
         else:
             n = lens.to(torch.int64)
             scored = (n + n % 256) >= 512 + 19 * 256
@@ -445,8 +410,8 @@ class PESQ(BaseMetric):
         rate = self.EXPECTED_SAMPLING_RATE
         if lengths is None and B:
             F = _cpu.pesq_frames(_cpu.resample64(clean[:1], sr, rate).shape[1])
-            if F < 20:  # as scores(): the reference's unfold(1, size=20, step=10) fails here (PESQ.py:169)
-                raise RuntimeError(f"maximum size for tensor at dimension 1 is {max(F, 0)} but size is 20")
+            if F < 20:  # as scores()
+                raise _too_short(F)
         nan = torch.full((1,), float("nan"), dtype=torch.float64)
         outs, scored = [], []
         for b in range(B):  # (a plain loop: each row's graph hangs on its own slice of `noisy`)
@@ -486,13 +451,7 @@ class PESQ(BaseMetric):
             raise ValueError(f"key must be one of {list(self.KEYS_LOSS)}, not {key!r}")
         mos, sym, asym, scored = self._differentiable(clean_speech, denoised_speech, sample_rate, lengths)
         score = -mos if key == "PESQ" else 0.1 * sym + 0.0309 * asym
-        scored = scored.to(score.device)
-        count = int(scored.sum())
-        total = torch.where(scored, score, torch.zeros((), dtype=score.dtype, device=score.device)).sum()
-        if count == 0:
-            # (an empty sum of the estimate: a zero on the graph, whose gradient is zero)
-            return total * 0 + torch.as_tensor(denoised_speech).reshape(-1)[:0].sum().to(total)
-        return total / count
+        return scored_mean(score, scored, denoised_speech)[0]
 
     def p862_scores(self, clean_speech: torch.Tensor, noisy_speech: torch.Tensor, lengths=None):
         """The ``time_align="p862"`` scores of 16 kHz rows (extension, not in the reference,
@@ -527,10 +486,9 @@ class PESQ(BaseMetric):
             _, sub = _wb_frames(lib, clean[rows], second[rows], None if lens is None else lens[rows])
             fr2[rows] = sub
         mos = torch.empty(B, dtype=torch.float32, device=clean.device)
-        _native.check(lib.fsem_pesq_pool_f32(fr1.data_ptr(), fr2.data_ptr(), ds.data_ptr(), B, L,
-                                             lens.data_ptr() if lens is not None else None, n_bad.data_ptr(),
-                                             bad.data_ptr(), mos.data_ptr(), _native.stream_handle(clean.device)),
-                      "PESQ pool")
+        _native.check(lib.fsem_pesq_pool_f32(fr1.data_ptr(), fr2.data_ptr(), ds.data_ptr(), B, L, _native.ptr(lens),
+                                             n_bad.data_ptr(), bad.data_ptr(), mos.data_ptr(),
+                                             _native.stream_handle(clean.device)), "PESQ pool")
         return mos, delays, n_bad, bad
 
     def compute_metric(self, clean_speech: torch.Tensor | None, denoised_speech: torch.Tensor,

@@ -45,7 +45,7 @@ class _EngineMatrices(torch.autograd.Function):
             src, est, ld = src.contiguous(), est.contiguous(), L
         sums = torch.empty(B, lib.fsem_pitsdr_sums_doubles(S, E, L, sample_rate), dtype=torch.float64, device=dev)
         rc = lib.fsem_pitsdr_f32(src.data_ptr(), est.data_ptr(), B, S, E, L, ld,
-                                 lens.data_ptr() if lens is not None else None, sample_rate, int(zero_mean), criterion,
+                                 _native.ptr(lens), sample_rate, int(zero_mean), criterion,
                                  sums.data_ptr(), si.data_ptr(), snr.data_ptr(), perm.data_ptr(),
                                  _native.stream_handle(dev))
         _native.check(rc, "PITSDR")
@@ -64,7 +64,7 @@ class _EngineMatrices(torch.autograd.Function):
         g_snr = g_snr.to(torch.float32).contiguous()
         lens = ctx.lens
         rc = _native.load().fsem_pitsdr_grad_f32(
-            ctx.src.data_ptr(), ctx.est.data_ptr(), B, S, E, L, ctx.ld, lens.data_ptr() if lens is not None else None,
+            ctx.src.data_ptr(), ctx.est.data_ptr(), B, S, E, L, ctx.ld, _native.ptr(lens),
             ctx.zero_mean, ctx.sums.data_ptr(), g_si.data_ptr(), g_snr.data_ptr(), grad.data_ptr(), L,
             _native.stream_handle(dev))
         _native.check(rc, "PITSDR backward")

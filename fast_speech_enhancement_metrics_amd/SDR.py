@@ -62,7 +62,7 @@ class SDR(BaseMetric):
             return tuple(out.fill_(float("nan")))
         ws = _native.workspace(lib.fsem_sdr_workspace_bytes(B, L, sr), clean.device)
         rc = lib.fsem_sdr_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                              lens.data_ptr() if lens is not None else None, sr, int(self.zero_mean),
+                              _native.ptr(lens), sr, int(self.zero_mean),
                               out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), ws.numel(),
                               _native.stream_handle(clean.device))
         _native.check(rc, "SDR")

@@ -65,7 +65,7 @@ class SRMR(BaseMetric):
         out = torch.empty(B, dtype=torch.float32, device=rows.device)
         energies = torch.empty(B, self.CHANNELS, self.MODS, dtype=torch.float64, device=rows.device)
         if B:
-            rc = lib.fsem_srmr_f32(rows.data_ptr(), B, L, rows.stride(0), lens.data_ptr() if lens is not None else None,
+            rc = lib.fsem_srmr_f32(rows.data_ptr(), B, L, rows.stride(0), _native.ptr(lens),
                                    self.sample_rate, energies.data_ptr(), out.data_ptr(),
                                    _native.stream_handle(rows.device))
             _native.check(rc, "SRMR")

@@ -18,8 +18,22 @@ import numpy as np
 import torch
 
 from . import _cpu, _native
-from .base import BaseMetric, as_rows, check_row_rate, device_lengths, noisy_shape, same_device, zero_tail
+from .base import (BaseMetric, check_row_rate, device_lengths, engine_rows, grad_buffer, grad_engine_rows,
+                   grad_operands, noisy_shape, pair_rows, scored_mean, zero_tail)
 from .batching import resampled_lengths
+
+NO_SEGMENT = "Not enough non-silent frames. Please check your sound files"  # (the reference's warning, STOI.py:162-165)
+
+
+def _bad_rate(sr: int) -> NotImplementedError:
+    return NotImplementedError(f"unsupported sample rate {sr}: its resampling filter to 10 kHz would be longer "
+                               "than 8192 taps (include/fsem.h, FSEM_ERATE)")
+
+
+def _check(rc: int) -> None:
+    if rc == _native.FSEM_ESHORT:
+        raise RuntimeError("STOI input shorter than one 256-sample frame at 10 kHz")
+    _native.check(rc, "STOI")
 
 
 class _EngineScores(torch.autograd.Function):
@@ -42,33 +56,24 @@ class _EngineScores(torch.autograd.Function):
             return s, e, seg
         nfloats = lib.fsem_stoi_state_floats(B, L, sr)
         if nfloats == 0:
-            raise NotImplementedError(f"unsupported sample rate {sr}: its resampling filter to 10 kHz would be longer "
-                                      "than 8192 taps (include/fsem.h, FSEM_ERATE)")
+            raise _bad_rate(sr)
         state = torch.empty(nfloats, dtype=torch.float32, device=dev)  # (not the shared workspace: it must outlive the call)
-        rc = lib.fsem_stoi_state_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                                     lens.data_ptr() if lens is not None else None, sr, s.data_ptr(), e.data_ptr(),
-                                     seg.data_ptr(), state.data_ptr(), _native.stream_handle(dev))
-        if rc == _native.FSEM_ESHORT:
-            raise RuntimeError("STOI input shorter than one 256-sample frame at 10 kHz")
-        _native.check(rc, "STOI")
+        _check(lib.fsem_stoi_state_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0), _native.ptr(lens), sr,
+                                       s.data_ptr(), e.data_ptr(), seg.data_ptr(), state.data_ptr(),
+                                       _native.stream_handle(dev)))
         ctx.state, ctx.noisy, ctx.lens, ctx.sr = state, noisy, lens, sr
         return s, e, seg
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_s, g_e, _g_seg):
-        B, L, width = ctx.shape
-        if ctx.state is None:
-            return torch.zeros(B, width, dtype=torch.float32, device=g_s.device), None, None, None, None
-        grad = torch.empty(B, width, dtype=torch.float32, device=g_s.device)  # (the entry writes [:, :L])
-        grad[:, L:] = 0
-        g_s = g_s.to(torch.float32).contiguous()
-        g_e = g_e.to(torch.float32).contiguous()
-        lens = ctx.lens
+        B, L, _ = ctx.shape
+        grad, g = grad_buffer(ctx.shape, ctx.state is not None, (g_s, g_e))
+        if g is None:
+            return grad, None, None, None, None
         rc = _native.load().fsem_stoi_grad_f32(
-            ctx.noisy.data_ptr(), B, L, ctx.noisy.stride(0), lens.data_ptr() if lens is not None else None, ctx.sr,
-            ctx.state.data_ptr(), g_s.data_ptr(), g_e.data_ptr(), grad.data_ptr(), grad.stride(0),
-            _native.stream_handle(g_s.device))
+            ctx.noisy.data_ptr(), B, L, ctx.noisy.stride(0), _native.ptr(ctx.lens), ctx.sr, ctx.state.data_ptr(),
+            g[0].data_ptr(), g[1].data_ptr(), grad.data_ptr(), grad.stride(0), _native.stream_handle(grad.device))
         _native.check(rc, "STOI backward")
         return grad, None, None, None, None
 
@@ -200,7 +205,7 @@ class STOI(BaseMetric):
         else:
             s, e = _cpu.rows_parallel(_cpu.stoi, torch.atleast_2d(clean_speech), torch.atleast_2d(denoised_speech))
         if bool(torch.isnan(s).all()):
-            warnings.warn("Not enough non-silent frames. Please check your sound files", RuntimeWarning, stacklevel=2)
+            warnings.warn(NO_SEGMENT, RuntimeWarning, stacklevel=2)
             return torch.tensor(0), torch.tensor(0)
         return s, e
 
@@ -222,11 +227,7 @@ class STOI(BaseMetric):
 
     def _rows_scores(self, clean_speech, denoised_speech, sr: int, lengths):
         """(stoi [B], estoi [B]) of rows at rate ``sr`` on their own device (one engine call)."""
-        clean = as_rows(clean_speech)
-        noisy = as_rows(denoised_speech)
-        if noisy.shape != clean.shape:
-            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
-        same_device(clean, noisy)
+        clean, noisy = pair_rows(clean_speech, denoised_speech)
         B, L = clean.shape
         if not clean.is_cuda:
             clean, noisy = clean.detach(), noisy.detach()  # scores are detached, as the engine's (differentiable_scores)
@@ -241,25 +242,16 @@ class STOI(BaseMetric):
                                           clean, noisy)
             return _cpu.rows_parallel(_cpu.stoi, clean, noisy)
         lib = _native.load()
-        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
-        if clean.stride(0) != noisy.stride(0) or L % 4:
-            # rows must be readable up to ceil4(L) floats (include/fsem.h): pad odd lengths
-            pad = (-L) % 4
-            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-            noisy = torch.nn.functional.pad(noisy, (0, pad)).contiguous()
+        clean, noisy, L, lens = engine_rows(clean, noisy, lengths)
         s = torch.empty(B, dtype=torch.float32, device=clean.device)
         e = torch.empty(B, dtype=torch.float32, device=clean.device)
         nbytes = lib.fsem_stoi_workspace_bytes(B, L, sr)
         if nbytes == 0:
-            raise NotImplementedError(f"unsupported sample rate {sr}: its resampling filter to 10 kHz would be longer "
-                                      "than 8192 taps (include/fsem.h, FSEM_ERATE)")
+            raise _bad_rate(sr)
         ws = _native.workspace(nbytes, clean.device)
-        rc = lib.fsem_stoi_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                               lens.data_ptr() if lens is not None else None, sr, s.data_ptr(),
-                               e.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_handle(clean.device))
-        if rc == _native.FSEM_ESHORT:
-            raise RuntimeError("STOI input shorter than one 256-sample frame at 10 kHz")
-        _native.check(rc, "STOI")
+        _check(lib.fsem_stoi_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0), _native.ptr(lens), sr,
+                                 s.data_ptr(), e.data_ptr(), ws.data_ptr(), ws.numel(),
+                                 _native.stream_handle(clean.device)))
         return s, e
 
     # ------------------------------------------------------------------ scores to train against
@@ -273,26 +265,10 @@ class STOI(BaseMetric):
             raise NotImplementedError("STOI: devices= is not supported with gradients (the multi-device fan-out "
                                       "returns detached scores)")
         sr = check_row_rate(self, sample_rate)
-        clean, noisy = torch.as_tensor(clean_speech), torch.as_tensor(denoised_speech)
-        if clean.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("STOI: the clean rows are constants; gradients with respect to `clean_speech` "
-                                      "are not supported (detach them)")
-        clean, noisy = torch.atleast_2d(clean.detach()), torch.atleast_2d(noisy)
-        if noisy.shape != clean.shape or clean.dim() != 2:
-            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
-        same_device(clean, noisy)
-        B, L = clean.shape
+        clean, noisy = grad_operands(self, clean_speech, denoised_speech)
         if not clean.is_cuda:
             return self._differentiable_cpu(clean, noisy, sr, lengths)
-        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
-        clean, rows = as_rows(clean), noisy.to(torch.float32)  # (autograd casts the gradient back)
-        if rows.stride(-1) != 1 or rows.stride(0) < L:
-            rows = rows.contiguous()
-        if clean.stride(0) != rows.stride(0) or L % 4:
-            # rows must be readable up to ceil4(L) floats (include/fsem.h): pad odd lengths
-            pad = (-L) % 4
-            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-            rows = torch.nn.functional.pad(rows, (0, pad)).contiguous()
+        clean, rows, L, lens = grad_engine_rows(clean, noisy, lengths)
         return _EngineScores.apply(rows, clean, lens, L, sr)
 
     def _differentiable_cpu(self, clean, noisy, sr: int, lengths):
@@ -337,14 +313,11 @@ class STOI(BaseMetric):
             raise ValueError(f"key must be one of {list(self.KEYS_LOSS)}, not {key!r}")
         s, e, seg = self._differentiable(clean_speech, denoised_speech, sample_rate, lengths)
         score = s if key == "STOI" else e
-        scored = seg.to(score.device) > 0
-        count = int(scored.sum())
-        total = torch.where(scored, score, torch.zeros((), dtype=score.dtype, device=score.device)).sum()
+        mean, count = scored_mean(score, seg.to(score.device) > 0, denoised_speech)
         if count == 0:
-            warnings.warn("Not enough non-silent frames. Please check your sound files", RuntimeWarning, stacklevel=2)
-            # (an empty sum of the estimate: a zero on the graph, whose gradient is zero)
-            return total + torch.as_tensor(denoised_speech).reshape(-1)[:0].sum().to(total)
-        return -total / count
+            warnings.warn(NO_SEGMENT, RuntimeWarning, stacklevel=2)
+            return mean
+        return -mean
 
     def _finish(self, stois: torch.Tensor, estois: torch.Tensor) -> list[dict[str, float]]:
         t = torch.stack([stois.float(), estois.float()])
@@ -354,7 +327,7 @@ class STOI(BaseMetric):
         else:
             res, nan_all = None, bool(torch.isnan(t[0]).all())
         if nan_all:  # no utterance has a 30-frame segment (STOI.py:162-165)
-            warnings.warn("Not enough non-silent frames. Please check your sound files", RuntimeWarning, stacklevel=3)
+            warnings.warn(NO_SEGMENT, RuntimeWarning, stacklevel=3)
             raise TypeError("iteration over a 0-d tensor")
         return res if res is not None else _native.score_list(t, ("STOI", "ESTOI"))
 

@@ -80,7 +80,7 @@ class SpectralMeasures(BaseMetric):
             out.fill_(float("nan"))
         else:
             rc = lib.fsem_spectral_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                                       lens.data_ptr() if lens is not None else None, sr, frames.data_ptr(), ldf,
+                                       _native.ptr(lens), sr, frames.data_ptr(), ldf,
                                        *(out[k].data_ptr() for k in range(3)), _native.stream_handle(clean.device))
             _native.check(rc, "SpectralMeasures")
         cols = tuple(out[k] for k in range(3))

@@ -468,8 +468,9 @@ def stream_handle(device: torch.device | None = None) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def ptr(t: torch.Tensor) -> int:
-    return t.data_ptr()
+def ptr(t: torch.Tensor | None) -> int | None:
+    """An optional operand for the C ABI: the tensor's address, or None (NULL) without one."""
+    return t.data_ptr() if t is not None else None
 
 
 def workspace(nbytes: int, device) -> torch.Tensor:

@@ -38,7 +38,7 @@ from __future__ import annotations
 import torch
 
 from . import _cpu, _native
-from .base import as_rows, device_lengths, same_device
+from .base import device_lengths, pair_rows
 
 DEFAULT_MAX_DELAY = 16000  # samples at 16 kHz (1 s)
 
@@ -47,11 +47,7 @@ MODES = ("row", "utterance", "p862")
 
 
 def _prepare(clean, noisy, max_delay):
-    c = as_rows(clean)
-    n = as_rows(noisy)
-    if c.shape != n.shape:
-        raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
-    same_device(c, n)
+    c, n = pair_rows(clean, noisy)
     if max_delay < 0:
         raise ValueError("max_delay must be >= 0")
     return c, n, min(int(max_delay), 2**31 - 1)  # the C-ABI's int32
@@ -96,7 +92,7 @@ def time_align(clean: torch.Tensor, noisy: torch.Tensor, lengths=None,
     delays = torch.empty(B, dtype=torch.int32, device=c.device)
     ws = _native.workspace(lib.fsem_time_align_workspace_bytes(B, L), c.device)
     _native.check(lib.fsem_time_align_f32(c.data_ptr(), n.data_ptr(), B, L, c.stride(0),
-                                          lens.data_ptr() if lens is not None else None, max_delay,
+                                          _native.ptr(lens), max_delay,
                                           delays.data_ptr(), out.data_ptr(), out.stride(0), ws.data_ptr(),
                                           ws.numel(), _native.stream_handle(c.device)), "time alignment")
     return out, delays
@@ -130,7 +126,7 @@ def time_align_segments(clean: torch.Tensor, noisy: torch.Tensor, lengths=None,
     wsb, entry = ((lib.fsem_time_align_p862_workspace_bytes, lib.fsem_time_align_p862_f32) if mode == "p862"
                   else (lib.fsem_time_align_utt_workspace_bytes, lib.fsem_time_align_utt_f32))
     ws = _native.workspace(wsb(B, L), c.device)
-    _native.check(entry(c.data_ptr(), n.data_ptr(), B, L, c.stride(0), lens.data_ptr() if lens is not None else None,
+    _native.check(entry(c.data_ptr(), n.data_ptr(), B, L, c.stride(0), _native.ptr(lens),
                         max_delay, delays.data_ptr(), nseg.data_ptr(), starts.data_ptr(), sdel.data_ptr(),
                         out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(), _native.stream_handle(c.device)),
                   "time alignment")
@@ -179,7 +175,7 @@ def realign_bad_intervals(clean: torch.Tensor, noisy: torch.Tensor, aligned: tor
         raise ValueError(f"n_seg must lie in [0, {S}]")
     ws = _native.workspace(lib.fsem_pesq_bad_intervals_workspace_bytes(B, L), c.device)
     _native.check(lib.fsem_pesq_bad_intervals_f32(c.data_ptr(), n.data_ptr(), a.data_ptr(), B, L, c.stride(0),
-                                                  lens.data_ptr() if lens is not None else None, frames.data_ptr(),
+                                                  _native.ptr(lens), frames.data_ptr(),
                                                   segs[0].data_ptr(), segs[1].data_ptr(), segs[2].data_ptr(),
                                                   n_bad.data_ptr(), bad.data_ptr(), second.data_ptr(), a.stride(0),
                                                   ws.data_ptr(), ws.numel(), _native.stream_handle(c.device)),

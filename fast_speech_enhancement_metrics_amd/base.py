@@ -215,6 +215,55 @@ def engine_rows(clean: torch.Tensor, noisy: torch.Tensor, lengths, *, empty_as_z
     return clean, noisy, L, lens
 
 
+# ---- the scores to train against (STOI.loss, PESQ.loss): what their host paths share
+
+def grad_operands(metric, clean_speech, denoised_speech):
+    """(clean.detach(), noisy) of a ``differentiable_scores`` / ``loss`` call, 2-D, of one shape, on
+    one device; ``noisy`` keeps its dtype, its layout and its graph."""
+    clean, noisy = torch.as_tensor(clean_speech), torch.as_tensor(denoised_speech)
+    if clean.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{type(metric).__name__}: the clean rows are constants; gradients with respect "
+                                  "to `clean_speech` are not supported (detach them)")
+    clean, noisy = torch.atleast_2d(clean.detach()), torch.atleast_2d(noisy)
+    if noisy.shape != clean.shape or clean.dim() != 2:
+        raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
+    same_device(clean, noisy)
+    return clean, noisy
+
+
+def grad_engine_rows(clean: torch.Tensor, noisy: torch.Tensor, lengths):
+    """grad_operands' CUDA rows as engine_rows gives them, (clean, rows, L, lens), with ``rows`` the
+    estimate in float32 on its graph (autograd casts the gradient back, and drops the padding)."""
+    rows = noisy.to(torch.float32)
+    if rows.stride(-1) != 1 or rows.stride(0) < rows.shape[1]:
+        rows = rows.contiguous()
+    return engine_rows(as_rows(clean), rows, lengths)
+
+
+def scored_mean(score: torch.Tensor, scored: torch.Tensor, estimate):
+    """(mean of ``score`` [B] over the rows ``scored`` [B] bool marks on its device, their count); with no such row
+    the mean is a zero on the graph of ``estimate`` (the estimate as the caller gave it), whose
+    gradient is zero."""
+    count = int(scored.sum())
+    total = torch.where(scored, score, torch.zeros((), dtype=score.dtype, device=score.device)).sum()
+    if count == 0:  # (an empty sum of the estimate)
+        return total * 0 + torch.as_tensor(estimate).reshape(-1)[:0].sum().to(total), 0
+    return total / count, count
+
+
+def grad_buffer(shape, launched: bool, upstream):
+    """What a gradient entry writes and reads, (grad [B, width] float32 with [:, L:] zero -- the entry
+    writes [:, :L] --, ``upstream`` as contiguous float32), for ``shape`` = (B, L, width); all of
+    ``grad`` zero and no upstream (None) when the forward launched nothing."""
+    B, L, width = shape
+    dev = upstream[0].device
+    if not launched:
+        return torch.zeros(B, width, dtype=torch.float32, device=dev), None
+    grad = torch.empty(B, width, dtype=torch.float32, device=dev)
+    grad[:, L:] = 0
+    return grad, [g.to(torch.float32).contiguous() for g in upstream]
+
+
 def noisy_shape(x) -> tuple:
     return tuple(torch.atleast_2d(torch.as_tensor(x)).shape) if x is not None else ()
 

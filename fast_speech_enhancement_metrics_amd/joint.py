@@ -17,8 +17,8 @@ import torch
 
 from . import _native
 from .PESQ import PESQ
-from .STOI import STOI
-from .base import BaseMetric, as_rows, check_row_rate, device_lengths, noisy_shape, same_device
+from .STOI import NO_SEGMENT, STOI
+from .base import BaseMetric, check_row_rate, device_lengths, engine_rows, noisy_shape, pair_rows
 
 
 _KEYS = ("PESQ", "STOI", "ESTOI")
@@ -70,27 +70,18 @@ class PESQ_STOI(BaseMetric):
 
     def _rows_scores(self, clean_speech, denoised_speech, lengths):
         """(mos, stoi, estoi) [B] of 16 kHz rows on their own device (one fused engine call)."""
-        clean = as_rows(clean_speech)
-        noisy = as_rows(denoised_speech)
-        if noisy.shape != clean.shape:
-            raise Exception("`clean_speech` and `denoised_speech` should have the same shape.")
-        same_device(clean, noisy)
-        B, L = clean.shape
+        clean, noisy = pair_rows(clean_speech, denoised_speech)
+        B = clean.shape[0]
         if not clean.is_cuda:
             mos = self._pesq.scores(clean, noisy, lengths, sample_rate=16000)
             s, e = self._stoi.scores(clean, noisy, 16000, lengths=lengths)
             return mos, s, e
         lib = _native.load()
-        lens = device_lengths(lengths, B, L, clean.device) if lengths is not None else None
-        if clean.stride(0) != noisy.stride(0) or L % 4:
-            pad = (-L) % 4  # rows readable up to ceil4(L) floats (include/fsem.h)
-            clean = torch.nn.functional.pad(clean, (0, pad)).contiguous()
-            noisy = torch.nn.functional.pad(noisy, (0, pad)).contiguous()
+        clean, noisy, L, lens = engine_rows(clean, noisy, lengths)
         out = torch.empty(3, B, dtype=torch.float32, device=clean.device)
         ws = _native.workspace(lib.fsem_pesq_stoi_workspace_bytes(B, L), clean.device)
-        rc = lib.fsem_pesq_stoi_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0),
-                                    lens.data_ptr() if lens is not None else None, out[0].data_ptr(),
-                                    out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), ws.numel(),
+        rc = lib.fsem_pesq_stoi_f32(clean.data_ptr(), noisy.data_ptr(), B, L, clean.stride(0), _native.ptr(lens),
+                                    out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), ws.numel(),
                                     _native.stream_handle(clean.device))
         if rc == _native.FSEM_ESHORT:
             # the reference's PESQ raises first for short inputs (its unfold, PESQ.py:169)
@@ -218,7 +209,7 @@ class PESQ_STOI(BaseMetric):
                     ev.synchronize()
                     _native.score_list_fill(h, lo, pinned[3 * lo:3 * hi].view(3, hi - lo).numpy(), _KEYS)
         if all(d["STOI"] != d["STOI"] for d in res):  # as STOI (STOI.py:162-165)
-            warnings.warn("Not enough non-silent frames. Please check your sound files", RuntimeWarning, stacklevel=4)
+            warnings.warn(NO_SEGMENT, RuntimeWarning, stacklevel=4)
         return res, out.t()
 
     def chunk_bounds(self, batch: int, on_gpu: bool = True) -> list[tuple[int, int]]:

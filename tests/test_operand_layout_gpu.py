@@ -1,17 +1,19 @@
 """The pair metrics' shared operand preparation (base.pair_rows, base.engine_rows) on the GPU: the
-scores of SDR, Composite, LSD and BSSSDR do not depend on how the operands lie in memory, and rows
-of no samples score as each metric documents.
+scores of SDR, Composite, LSD, BSSSDR, PESQ, STOI and the joint PESQ_STOI do not depend on how the
+operands lie in memory, and rows of no samples score as each metric documents.
 
 The engine headers promise scores independent of alignment and row capacity, so the reference is
 the call on contiguous operands and the comparison is bitwise.  The layouts take every branch of
 the padding rule: an odd element offset (bases not 16-byte aligned), different row strides for the
 two operands, and a row stride that is no multiple of 4.  Every length but 260 is no multiple of 4
-and is padded whatever the layout; at 260 (and Composite's 5248) the views themselves reach the
-engine unless the rule (or its 16-byte form) copies them."""
+and is padded whatever the layout; at 260 (and Composite's 5248, and the 8196 of PESQ, STOI and the
+joint call) the views themselves reach the engine unless the rule (or its 16-byte form) copies them.
+PESQ, STOI and the joint call are scored at lengths that give every row a finite score (PESQ needs
+20 frames, STOI a 30-frame segment at 10 kHz), so their comparison is one of numbers, not of NaNs."""
 import pytest
 import torch
 
-from fast_speech_enhancement_metrics_amd import BSSSDR, DNSMOS, LSD, SDR, Composite, _cpu
+from fast_speech_enhancement_metrics_amd import BSSSDR, DNSMOS, LSD, PESQ, PESQ_STOI, SDR, STOI, Composite, _cpu
 
 from . import lsd_cases as lc
 
@@ -23,6 +25,10 @@ LENGTHS = (1, 5, 258, 260, 8193)
 SHORTEST = next(L for L in range(1, 1 << 14) if _cpu.pesq_frames(L) >= 20)
 METRICS = {"SDR": (SDR, LENGTHS), "Composite": (Composite, (SHORTEST, SHORTEST + 1)), "LSD": (LSD, LENGTHS),
            "BSSSDR": (BSSSDR, LENGTHS)}
+FINITE = (8193, 8196)  # every row of rows() has 20 PESQ frames and 8 STOI segments at both
+METRICS.update({"PESQ": (PESQ, FINITE), "STOI": (STOI, FINITE), "PESQ_STOI": (PESQ_STOI, FINITE)})
+# (a STOI(16000)'s scores() must be told its rows' rate)
+RATE = {"STOI": (16000,)}
 
 
 def rows(L: int):
@@ -64,14 +70,17 @@ def assert_same(got: torch.Tensor, want: torch.Tensor, what: str) -> None:
 def test_scores_do_not_depend_on_the_operands_layout(name):
     cls, lengths = METRICS[name]
     metric = cls(16000, use_gpu=True)
+    rate = RATE.get(name, ())
     for L in lengths:
         c, n = rows(L)
         assert c.is_contiguous() and n.is_contiguous()
-        want = stacked(metric.scores(c, n))
+        want = stacked(metric.scores(c, n, *rate))
         assert want.shape[-1] == B
+        if lengths is FINITE:
+            assert want.isfinite().all(), (name, L, want)
         for what, cv, nv in layouts(c, n):
-            assert_same(stacked(metric.scores(cv, nv)), want, f"{name} L={L}: {what}")
-        assert_same(stacked(metric.scores(c, n)), want, f"{name} L={L}: repeated")
+            assert_same(stacked(metric.scores(cv, nv, *rate)), want, f"{name} L={L}: {what}")
+        assert_same(stacked(metric.scores(c, n, *rate)), want, f"{name} L={L}: repeated")
 
 
 def test_rows_of_no_samples():
