@@ -20,10 +20,10 @@ import functools
 
 import numpy as np
 import torch
-from scipy.signal import lfilter, sosfilt
-
-from fast_speech_enhancement_metrics_amd import _cpu, synthetic
+from fast_speech_enhancement_metrics_amd import synthetic
 from fast_speech_enhancement_metrics_amd import _tables as T
+
+from .stage_cases import _bark, frames_of  # noqa: F401  (one copy, shared with the stage tests)
 
 SEED = 7
 ALPHA = (1.0, 0.3, 0.1, 0.03)
@@ -69,57 +69,6 @@ def rows(name: str):
         d[1, 5000] = float("nan")
         return c, d
     raise KeyError(name)
-
-
-def frames_of(L: int) -> int:
-    Lp = L + L % 256
-    return 0 if Lp < 512 else 1 + (Lp - 512) // 256
-
-
-_EDGES = np.concatenate([[0], np.cumsum(T.BINS_PER_BAND)])
-_PRE = (np.asarray(T.PRE_B, np.float32), np.asarray(T.PRE_A, np.float32))
-
-
-class _Filter(torch.autograd.Function):
-    """One of the two IIRs on a 1-D row from zero state and its adjoint: the same filter on the time-reversed
-    gradient.  The recursion itself runs in float64 and its output is rounded to the row's dtype: scipy's
-    float32 direct form forms b0 x[n] - 2 b0 x[n-1] + b0 x[n-2] from three rounded products and loses the low
-    frequencies' digits there (measured: it alone puts the float32 restatement's error at 2e-3, 20 times the rest
-    of the chain's), which is that evaluation order's error, not the format's; the engine takes the second
-    difference exactly (csrc/pesq.hip, pre_fir).  This choice only tightens the bar."""
-
-    @staticmethod
-    def run(x, kind):
-        v = x.detach().numpy()
-        if kind == "bp":
-            return torch.from_numpy(sosfilt(_cpu._BP_SOS, v.astype(np.float64)).astype(v.dtype))
-        return torch.from_numpy(lfilter(_PRE[0].astype(np.float64), _PRE[1].astype(np.float64),
-                                        v.astype(np.float64)).astype(v.dtype))
-
-    @staticmethod
-    def forward(ctx, x, kind):
-        ctx.kind = kind
-        return _Filter.run(x, kind)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _Filter.run(g.flip(0), ctx.kind).flip(0), None
-
-
-def _bark(x, dtype):
-    """[L] -> Bark bands [F, 49] after level alignment, taper and pre-emphasis."""
-    L = x.numel()
-    u = _Filter.apply(x, "bp")
-    s = x * torch.sqrt(1e7 / ((u * u).sum() / (L + 5120) / 1.04684))
-    w = torch.ones(L, dtype=dtype)
-    w[:15] = torch.arange(1, 16, dtype=dtype) / 16
-    w[-15:] = torch.arange(15, 0, -1, dtype=dtype) / 16
-    s = torch.nn.functional.pad(_Filter.apply(s * w, "pre"), (0, L % 256))
-    z = torch.fft.rfft(s.unfold(0, 512, 256) * torch.hann_window(512, dtype=dtype), dim=1)
-    p = z.real.square() + z.imag.square()
-    corr = torch.tensor(T.POW_DENS_CORRECTION, dtype=torch.float64) * T.SP_16K
-    bands = [p[:, max(int(lo), 1):int(hi)].sum(1) for lo, hi in zip(_EDGES[:-1], _EDGES[1:])]   # (bin 0 is zeroed)
-    return torch.stack(bands, 1) * corr.to(dtype)
 
 
 def restated(clean_row, est_row, dtype, probe=None):
