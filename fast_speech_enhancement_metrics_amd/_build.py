@@ -37,9 +37,9 @@ _ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # (pesq_back.hip) keeps it: its 49-band loops pack into fewer instructions with it, and so does
 # the backward (pesq_grad.hip), whose row kernel has the same band loops.
 SOURCE_FLAGS = {"pesq.hip": ["-fno-slp-vectorize"], "stoi.hip": _ILP, "resample.hip": _ILP}
-HEADERS = ["fsem_build_marker.h", "fsem_common.h", "fsem_corr512.h", "fsem_fft.h", "fsem_internal.h", "fsem_lpc.h",
-           "fsem_pesq.h", "fsem_resample.h", "fsem_select.h", "fsem_speech_frames.h", "fsem_stoi.h", "fsem_tables.inc",
-           "fsem_vad.h"]
+HEADERS = ["fsem_build_marker.h", "fsem_common.h", "fsem_complex.h", "fsem_corr512.h", "fsem_fft.h",
+           "fsem_internal.h", "fsem_lpc.h", "fsem_pesq.h", "fsem_resample.h", "fsem_sdr_rules.h", "fsem_select.h",
+           "fsem_speech_frames.h", "fsem_stoi.h", "fsem_tables.inc", "fsem_vad.h"]
 HEADER_ABI = os.path.join(PKG, "..", "include", "fsem.h")
 COMPOSITE_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_composite.h")
 LSD_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_lsd.h")

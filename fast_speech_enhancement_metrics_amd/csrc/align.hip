@@ -43,6 +43,7 @@
 // The other stages are O(L) or O(M * L / 64).
 #include "fsem_common.h"
 #include "fsem_fft.h"
+#include "fsem_pesq.h"
 
 namespace fsem {
 namespace align {
@@ -1104,12 +1105,6 @@ constexpr int BAD_MIN = 5;       // frames: shorter intervals are dropped
 constexpr int MAXBAD = 16;       // intervals per row (include/fsem.h FSEM_PESQ_MAX_BAD)
 constexpr int HOP = 256;         // samples per PESQ frame hop
 
-// PESQ frames of a row (fsem_pesq_frames: PESQ.py:128-133 pads by L % 256, 512-sample frames)
-__host__ __device__ inline int pesq_frames_of(int64_t L) {
-  const int64_t Lp = L + (L % 256);
-  return Lp < 512 ? 0 : (int)(1 + (Lp - 512) / 256);
-}
-
 // One wave per row: the symmetric disturbances 64 frames at a time (a ballot of the bad frames),
 // the runs walked with bit scans in wave-uniform code as ta_utterances; then (lane 0) each
 // interval's samples [256 f0, min(256 f1 + 256, L_row)), the delay of the segment holding its
@@ -1125,7 +1120,7 @@ __global__ void __launch_bounds__(64) ta_bad_find(int64_t B, int64_t L, const in
   if (b >= B) return;
   const int lane = threadIdx.x;
   const int64_t Lr = row_length(lengths, b, L);
-  const int F = std::min<int64_t>(pesq_frames_of(Lr), Fcap);
+  const int F = std::min<int64_t>(pesq::frames_of(Lr), Fcap);
   const float *sym = frames + 2 * b * Fcap;
   int n = 0, s0 = -1, e0 = -1, rs = -1;  // intervals, joined run [s0, e0), open raw run from rs
   auto flush = [&]() {
@@ -1271,7 +1266,7 @@ __global__ void __launch_bounds__(256) ta_bad_shift(const float *__restrict__ de
 
 // One wave per row: each interval takes the second row's frames when their symmetric sum is
 // smaller (double, wave order), then PESQ.py:168-172's pooling and :240-243's mapping as
-// pesq_back's pass 3 (windows lane-strided, wave sums in double).
+// pesq_back's pass 3 (window_l6 and mos_of, fsem_pesq.h; windows lane-strided, wave sums in double).
 __global__ void __launch_bounds__(64) ta_bad_pool(const float *__restrict__ frames, const float *__restrict__ frames2,
                                                   const float *__restrict__ dist, int64_t B, int64_t L,
                                                   int64_t Fcap, const int32_t *__restrict__ lengths,
@@ -1282,7 +1277,7 @@ __global__ void __launch_bounds__(64) ta_bad_pool(const float *__restrict__ fram
   if (b >= B) return;
   const int lane = threadIdx.x;
   const int64_t Lr = row_length(lengths, b, L);
-  const int F = std::min<int64_t>(pesq_frames_of(Lr), Fcap);
+  const int F = std::min<int64_t>(pesq::frames_of(Lr), Fcap);
   if (F < 20 || !__builtin_isfinite(dist[b])) {
     if (lane == 0) mos[b] = __builtin_nanf("");
     return;
@@ -1312,17 +1307,15 @@ __global__ void __launch_bounds__(64) ta_bad_pool(const float *__restrict__ fram
   const int nw = (F - 20) / 10 + 1;
   double as_ = 0.0, aa_ = 0.0;
   for (int w = lane; w < nw; w += 64) {
-    double s6 = 0.0, a6 = 0.0;
-    for (int i = 0; i < 20; ++i) {
-      const int f = 10 * w + i;
-      bool second = false;
-      for (int q = 0; q < nu; ++q) second |= (f >= f0s[q] && f < f1s[q]);
-      const double x = second ? s2[f] : s1[f], y = second ? a2[f] : a1[f];
-      const double x2 = x * x, y2 = y * y;
-      s6 += x2 * x2 * x2;
-      a6 += y2 * y2 * y2;
-    }
-    const double ps = pow(s6 / 20.0, 1.0 / 6.0), pa = pow(a6 / 20.0, 1.0 / 6.0);
+    double ps, pa;
+    pesq::window_l6(
+        w,
+        [&](int f, double &x, double &y) {
+          bool second = false;
+          for (int q = 0; q < nu; ++q) second |= (f >= f0s[q] && f < f1s[q]);
+          x = second ? s2[f] : s1[f], y = second ? a2[f] : a1[f];
+        },
+        ps, pa);
     as_ += ps * ps;
     aa_ += pa * pa;
   }
@@ -1330,9 +1323,7 @@ __global__ void __launch_bounds__(64) ta_bad_pool(const float *__restrict__ fram
   aa_ = wave_sum_d(aa_);
   if (lane == 0) {
     const double ds = sqrt(as_ / nw), da = sqrt(aa_ / nw);
-    double m = 4.5 - 0.1 * ds - 0.0309 * da;
-    m = 0.999 + 4.0 / (1.0 + exp(-1.3669 * m + 3.8224));
-    mos[b] = (float)m;
+    mos[b] = (float)pesq::mos_of(ds, da);
   }
 }
 
@@ -1574,7 +1565,7 @@ extern "C" int fsem_pesq_bad_intervals_f32(const float *ref, const float *deg, c
   const align::BadWs w = align::bad_layout(a, batch, length);
   if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t Fcap = align::pesq_frames_of(length);
+  const int64_t Fcap = pesq::frames_of(length);
   align::ta_bad_find<<<grid_xy(batch), 64, 0, st>>>(batch, length, lengths, frames, Fcap, n_seg, seg_start, seg_delay,
                                                     n_bad, bad, w.desc, w.ndesc, w.cs, (int)nsl);
   FSEM_CHECK_LAUNCH();
@@ -1597,7 +1588,7 @@ extern "C" int fsem_pesq_pool_f32(const float *frames, const float *frames2, con
                                   float *mos, void *stream) {
   if (!frames || !frames2 || !dist || !n_bad || !bad || !mos || batch <= 0 || length <= 0 || length > kMaxLength)
     return FSEM_EINVAL;
-  const int64_t Fcap = align::pesq_frames_of(length);
+  const int64_t Fcap = pesq::frames_of(length);
   if (Fcap < 20 && !lengths) return FSEM_ESHORT;
   align::ta_bad_pool<<<grid_xy(batch), 64, 0, (hipStream_t)stream>>>(frames, frames2, dist, batch, length, Fcap,
                                                                       lengths, n_bad, bad, mos);

@@ -130,6 +130,35 @@ __device__ __forceinline__ Len row_length(const int32_t *__restrict__ lens, int6
   return n < 0 ? 0 : (n > L ? L : n);
 }
 
+// A wave-uniform buffer descriptor over the nbytes bytes at p: raw buffer loads through it are
+// range checked by the hardware, a load past the end returns 0 without a branch.  The words go
+// through readfirstlane so that the descriptor sits in scalar registers (as uint32_t:
+// readfirstlane returns int, which would sign-extend into the high word).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void *p, uint32_t nbytes) {
+  const uint64_t base = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
+  void *q = reinterpret_cast<void *>(((uint64_t)hi << 32) | lo);
+  return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane(nbytes), 0x00020000);
+}
+// The float at byte offset voff + soff (soff wave-uniform) behind such a descriptor.
+__device__ __forceinline__ float buffer_f32(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff = 0) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0));
+}
+
+// Four consecutive samples of a row from sample a (a % 4 == 0), zeros from sample `hi` on.  VEC:
+// the row is 16-byte aligned, so four samples below hi are one float4.
+template <bool VEC>
+__device__ __forceinline__ void load4(const float *__restrict__ row, int a, int hi, float v[4]) {
+  if (VEC && a + 4 <= hi) {
+    const float4 x = *reinterpret_cast<const float4 *>(row + a);
+    v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = a + j < hi ? row[a + j] : 0.f;
+  }
+}
+
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // A workspace as a sequence of 256-byte aligned regions.  Each entry has one layout function

@@ -1,6 +1,6 @@
 // One-wave 512-point complex FFT (radix-8 Stockham) shared by the PESQ and STOI kernels.
 #pragma once
-#include "fsem_common.h"
+#include "fsem_complex.h"
 
 namespace fsem {
 #include "fsem_tables.inc"
@@ -8,42 +8,9 @@ namespace fsem {
 struct cf {
   float r, i;
 };
-__device__ __forceinline__ cf cadd(cf a, cf b) { return {a.r + b.r, a.i + b.i}; }
-__device__ __forceinline__ cf csub(cf a, cf b) { return {a.r - b.r, a.i - b.i}; }
-__device__ __forceinline__ cf cmul(cf a, cf b) {
-  return {fmaf(a.r, b.r, -a.i * b.i), fmaf(a.r, b.i, a.i * b.r)};
-}
-__device__ __forceinline__ cf mul_mi(cf a) { return {a.i, -a.r}; }  // a * (-i)
 
-// In-register forward DFT of 8 points (radix-2 DIT, W8 = exp(-i pi/4)).
-__device__ __forceinline__ void dft8(cf v[8]) {
-  const float h = 0.70710678118654752f;
-  cf a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]);
-  cf a2 = cadd(v[2], v[6]), a3 = mul_mi(csub(v[2], v[6]));
-  cf a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]);
-  cf a6 = cadd(v[3], v[7]), a7 = mul_mi(csub(v[3], v[7]));
-  cf b0 = cadd(a0, a2), b2 = csub(a0, a2), b1 = cadd(a1, a3), b3 = csub(a1, a3);
-  cf c0 = cadd(a4, a6), c2 = csub(a4, a6), c1 = cadd(a5, a7), c3 = csub(a5, a7);
-  cf w1c1 = {h * (c1.r + c1.i), h * (c1.i - c1.r)};    // c1 * (1 - i)/sqrt2
-  cf w3c3 = {h * (c3.i - c3.r), -h * (c3.r + c3.i)};   // c3 * (-1 - i)/sqrt2
-  cf mic2 = mul_mi(c2);
-  v[0] = cadd(b0, c0);
-  v[4] = csub(b0, c0);
-  v[1] = cadd(b1, w1c1);
-  v[5] = csub(b1, w1c1);
-  v[2] = cadd(b2, mic2);
-  v[6] = csub(b2, mic2);
-  v[3] = cadd(b3, w3c3);
-  v[7] = csub(b3, w3c3);
-}
-
-// LDS exchange area per wave: 512 float2, element i stored at fsw(i) = i ^ ((i >> 3) & 15).
-// The XOR swizzle keeps all four access patterns bank-conflict-free under the gfx950 LDS
-// lane-group rules (stage scatters 8*lane + r and o1 + 8r as ds_write_b64 in 16-lane groups,
-// gathers lane + 64r as ds_read_b64 in 32-lane groups) without padding; the former i + i/8
-// padding left 2-way conflicts on the gathers.
+// LDS exchange area per wave: 512 float2, element i stored at fpad(i) (fsem_complex.h).
 constexpr int kFftBuf = 512;
-__device__ __forceinline__ int fpad(int i) { return i ^ ((i >> 3) & 15); }
 
 // Packed-FP32 form of the butterflies: complex values as float2 vectors, so additions become
 // v_pk_add_f32 and the multiplications by -i, (1-i)/sqrt2, (-1-i)/sqrt2 fold into v_pk_fma_f32
@@ -226,6 +193,62 @@ __device__ __forceinline__ void fft512_twiddles(int lane, cf tw1[8], cf tw2[8]) 
     const int i2 = (r * lane) & 511;
     tw1[r] = {kTwRe[i1], kTwIm[i1]};
     tw2[r] = {kTwRe[i2], kTwIm[i2]};
+  }
+}
+
+// ---- two real frames per transform: v[r] = Z[lane + 64 r] of z = frame a + i frame b, whose
+// spectra are A = (Z[k] + conj Z[N-k]) / 2 and B = (Z[k] - conj Z[N-k]) / 2i (mirror_bin, fsem_complex.h).
+
+// pair_powers: 4 |A|^2 and 4 |B|^2 on bins k = lane + 64 r, r < 4, in packed FP32:
+// (pa, pb) = (|zr + mr|^2 + (zi - mi)^2, |zi + mi|^2 + (zr - mr)^2), the same per-element
+// operations as the scalar form, half the instructions.
+__device__ __forceinline__ void pair_powers(const cf v[8], int lane, int plane, float pa[4], float pb[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    // mirror_bin's body written out: through the call stoi_tob gains four s_waitcnt (static gate)
+    float mr = __shfl(v[7 - r].r, plane, 64);
+    float mi = __shfl(v[7 - r].i, plane, 64);
+    if (lane == 0) {
+      mr = v[(8 - r) & 7].r;
+      mi = v[(8 - r) & 7].i;
+    }
+    const f2 z = {v[r].r, v[r].i}, m = {mr, mi};
+    const f2 sm = z + m;
+    const f2 df = z.yx - m.yx;  // (zi - mi, zr - mr)
+    const f2 pp = FSEM_FMA2(sm, sm, df * df);
+    pa[r] = pp.x;
+    pb[r] = pp.y;
+  }
+}
+
+// pair_grad_fold: the backward of a per-bin weighting of both frames' spectra.  With Ga = ca 2 A
+// and Gb = cb 2 B on bins k = lane + 64 r, r < 4 -- coef(r, ca, cb) yields the frames' coefficients
+// there, 0 on bin 0 and on bins a caller leaves out -- it returns u[r] = W[lane + 64 r] with
+// W[k] = conj(Ga + i Gb) and W[N-k] = conj(conj Ga + i conj Gb); bin 256 is 0.  The forward
+// transform of W is conj(ga + i gb): the derivatives with respect to both frames' samples.
+// (The coefficients come from a callable evaluated bin by bin: taken as two arrays filled
+// beforehand, stoi_tob_grad's sums were vectorised with other fused multiply-adds, other bits.)
+template <class Coef>
+__device__ __forceinline__ void pair_grad_fold(const cf v[8], Coef coef, int lane, int plane, cf u[8]) {
+  cf wm[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const cf m = mirror_bin(v, r, lane, plane);
+    float ca, cb;
+    coef(r, ca, cb);
+    const cf Ga = {ca * (v[r].r + m.r), ca * (v[r].i - m.i)};
+    const cf Gb = {cb * (v[r].i + m.i), -cb * (v[r].r - m.r)};
+    u[r] = {Ga.r - Gb.i, -(Ga.i + Gb.r)};
+    wm[r] = {Ga.r + Gb.i, Ga.i - Gb.r};
+  }
+  wave_lds_fence();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) u[7 - r] = {__shfl(wm[r].r, plane, 64), __shfl(wm[r].i, plane, 64)};
+  if (lane == 0) {  // bins 64 r mirror to 64 (8 - r); bin 256 lies in no band
+    u[7] = wm[1];
+    u[6] = wm[2];
+    u[5] = wm[3];
+    u[4] = {0.f, 0.f};
   }
 }
 

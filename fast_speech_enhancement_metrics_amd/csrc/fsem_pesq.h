@@ -1,5 +1,7 @@
 // Shared geometry of the PESQ front end (pesq.hip) and back end (pesq_back.hip): frames,
-// segments and the band-major Bark layout of a row (PESQ.py:123-140, bark.py:189-204).
+// segments and the band-major Bark layout of a row (PESQ.py:123-140, bark.py:189-204); and the
+// device functions that the forward, the backward (pesq_grad.hip) and the time alignment's pooling
+// (align.hip) share.
 #pragma once
 #include "fsem_fft.h"  // (fsem_tables.inc: FSEM_PESQ_CH)
 
@@ -63,6 +65,67 @@ __device__ __forceinline__ float loud(float p, int b) {
   // branch-free (p >= 0: the pow argument is >= 0.5 either way)
   const float v = kLoud2TE[b] * (pow_pos(fmaf(p, kHalfInvThresh[b], 0.5f), kLoudExp[b]) - 1.f);
   return (p > kThresh[b]) ? v : 0.f;
+}
+
+// ---- the back end's arithmetic, shared by pesq_back (pesq_back.hip), its reverse pesq_back_grad
+// (pesq_grad.hip) and the time alignment's pooling (ta_bad_pool, align.hip).
+
+// PESQ.py:97-100 -- a signal's power = band-pass sum / (L + 5120) / 1.04684, and its samples (here:
+// its Bark bands) are scaled by 1e7 / power.
+__device__ __forceinline__ float level_scale(float pw, int64_t L) {
+  const float p = pw / (float)(L + 5120) / 1.04684f;
+  return 1e7f / p;
+}
+
+// One band of one frame (PESQ.py:186-224) from the level-equalised clean power ec and denoised
+// power en.  band_terms: the loudnesses lc, ln; their difference d0 and its magnitude past the
+// dead zone of a quarter of the smaller loudness, mag (the disturbance is mag's positive part with
+// d0's sign); wd, the disturbance times the band's width.  asymmetry_raw: ((en + 50) / (ec +
+// 50))^1.2 (~1 ulp rcp); asymmetry_factor: that, 0 below 3 and at most 12.  A frame's symmetric
+// sum takes wd^2, its asymmetric sum |wd am|.  (wd and am as two calls, the symmetric sum's
+// update between them: as one function returning both, pesq_back fails the static gate.)
+struct BandTerms {
+  float lc, ln, d0, mag, wd;
+};
+__device__ __forceinline__ BandTerms band_terms(float ec, float en, int k) {
+  BandTerms o;
+  o.lc = loud(ec, k), o.ln = loud(en, k);
+  o.d0 = o.ln - o.lc;
+  const float dz = 0.25f * fminf(o.lc, o.ln);
+  o.mag = fabsf(o.d0) - dz;
+  o.wd = kWidthBark[k] * copysignf(fmaxf(o.mag, 0.f), o.d0);
+  return o;
+}
+__device__ __forceinline__ float asymmetry_raw(float ec, float en) {
+  return pow_pos((en + 50.f) * __builtin_amdgcn_rcpf(ec + 50.f), 1.2f);
+}
+__device__ __forceinline__ float asymmetry_factor(float am0) { return (am0 < 3.f) ? 0.f : fminf(am0, 12.f); }
+
+// L6 norms of window w's 20 frames (hop 10) of the symmetric and the asymmetric frame
+// disturbances, in double (PESQ.py:168-170); frame(f, x, y) yields frame f's two.  The callers add
+// the squares up over the windows (L2, :171-172).
+template <class Frame>
+__device__ __forceinline__ void window_l6(int w, Frame frame, double &ps, double &pa) {
+  double s6 = 0.0, a6 = 0.0;
+  for (int i = 0; i < 20; ++i) {
+    double x, y;
+    frame(10 * w + i, x, y);
+    const double x2 = x * x, y2 = y * y;
+    s6 += x2 * x2 * x2;
+    a6 += y2 * y2 * y2;
+  }
+  ps = pow(s6 / 20.0, 1.0 / 6.0);
+  pa = pow(a6 / 20.0, 1.0 / 6.0);
+}
+
+// The distances' mapping to MOS-LQO: raw = 4.5 - 0.1 ds - 0.0309 da (PESQ.py:240), then
+// 0.999 + 4 / (1 + exp(-1.3669 raw + 3.8224)) (PESQ.py:243).
+constexpr double kMosBase = 4.5, kMosSym = 0.1, kMosAsym = 0.0309;
+constexpr double kMosLo = 0.999, kMosSpan = 4.0, kMosSlope = 1.3669, kMosShift = 3.8224;
+__device__ __forceinline__ double mos_raw(double ds, double da) { return kMosBase - kMosSym * ds - kMosAsym * da; }
+__device__ __forceinline__ double mos_exp(double raw) { return exp(-kMosSlope * raw + kMosShift); }
+__device__ __forceinline__ double mos_of(double ds, double da) {
+  return kMosLo + kMosSpan / (1.0 + mos_exp(mos_raw(ds, da)));
 }
 
 // Workspace layouts (Arena, fsem_common.h).

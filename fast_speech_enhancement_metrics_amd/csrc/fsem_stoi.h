@@ -1,6 +1,7 @@
 // Declarations shared by the STOI engine (stoi.hip) and its backward (stoi_grad.hip): the
-// constants of the metric, the per-row lengths, the geometry of a call and the forward's
-// workspace layout, which the backward reads as its state.
+// constants of the metric, the per-row lengths, the geometry of a call, the forward's
+// workspace layout, which the backward reads as its state, and the device code by which
+// stoi_tob and stoi_tob_grad build the same frame pairs.
 #pragma once
 #include "fsem_fft.h"
 #include "fsem_resample.h"
@@ -64,6 +65,64 @@ __device__ __forceinline__ uint32_t peak_exponents(float c0, float c1, float c2,
   e = pmax(e, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e, 0x142, 0xA, 0xF, false));
   e = pmax(e, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e, 0x143, 0xC, 0xF, false));
   return __builtin_amdgcn_readlane(e, 63);
+}
+
+// ---- what stoi_tob and its backward stoi_tob_grad both do to one signal: the backward has to
+// rebuild exactly the frame pairs the forward transformed.
+
+// Sample o of a 10 kHz row through a range-checked descriptor over its [0, L10) (row_rsrc over
+// L10 * 4 bytes): samples past the row end read as 0 without a branch per load (torchaudio's zero
+// padding of the overlap-added signal).
+__device__ __forceinline__ float sample_at(__amdgpu_buffer_rsrc_t r, int64_t o) { return buffer_f32(r, (int)(o * 4)); }
+
+// This lane's four values of the 256-point Hann window: w[lane], w[64 + lane], w[128 + lane],
+// w[192 + lane] -- the STFT window on a frame's 256 samples (v[r] takes win[r]), and the
+// overlap-add weights of a block's two halves.
+__device__ __forceinline__ void hann_quad(int lane, float win[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) win[r] = kHann256s[lane + 64 * r];
+}
+
+// Overlap-added block q of the kept frames kidx: block_q[t] = w[t] F_{i_q}[t] + w[128 + t]
+// F_{i_{q-1}}[128 + t], F_i = the row's samples from 128 i.  ola_taps loads this lane's four
+// samples (t = lane and 64 + lane of both frames), ola_block combines them into block_q[64 h +
+// lane]; apart, so that a caller can have several blocks' loads in flight.
+__device__ __forceinline__ void ola_taps(__amdgpu_buffer_rsrc_t r, const int *kidx, int q, int lane, float g[4]) {
+  const int64_t a0 = 128LL * kidx[q], a1 = 128LL * kidx[q - 1] + 128;
+  g[0] = sample_at(r, a0 + lane);
+  g[1] = sample_at(r, a1 + lane);
+  g[2] = sample_at(r, a0 + 64 + lane);
+  g[3] = sample_at(r, a1 + 64 + lane);
+}
+__device__ __forceinline__ float ola_block(const float win[4], const float g[4], int h) {
+  return win[h] * g[2 * h] + win[2 + h] * g[2 * h + 1];
+}
+
+// Both kernels then transform two consecutive STFT frames of ONE signal as z = frame a + i frame
+// b, frame a = [block_ja, block_ja+1] * w, zero-padded to 512 points.  That load stays written out
+// in both: as a function (whole, per point, block rows by pointer or by reference) it fails
+// stoi_tob's static gate (SALU 391 -> 389, s_waitcnt 106 -> 113).
+
+// The frame pair's peak exponents (peak_exponents): ea of frame a, the real parts, eb of frame b.
+__device__ __forceinline__ void pair_peaks(const cf v[8], int &ea, int &eb) {
+  const uint32_t pk = peak_exponents(v[0].r, v[1].r, v[2].r, v[3].r, v[0].i, v[1].i, v[2].i, v[3].i);
+  ea = (int)(pk >> 16), eb = (int)(pk & 0xffffu);
+}
+
+// The shared transform's rounding is not exactly Hermitian: it leaks ~1e-7 of the louder frame's
+// spectrum into the quieter one's, so a frame ~100 dB or more below its neighbour (an onset after
+// silence) would lose its spectrum to the leak.  Pairs with a gap of 2^7 or more in peak sample
+// are equalised first: frame b is scaled by 2^sh to frame a's peak exponent (exact in floating
+// point; |sh| at most 60), and the caller scales what it derives from frame b's spectrum by 2^-sh
+// after the transform (exact again).  Returns sh, 0 for a pair left as it is.
+__device__ __forceinline__ int pair_level_shift(cf v[8], int ea, int eb) {
+  int sh = (ea > 0 && eb > 0) ? ea - eb : 0;
+  sh = (sh >= 7 || sh <= -7) ? max(-60, min(60, sh)) : 0;
+  if (sh != 0) {  // uniform
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r].i = __builtin_amdgcn_ldexpf(v[r].i, sh);
+  }
+  return sh;
 }
 
 #ifndef FSEM_SEG_T

@@ -36,7 +36,7 @@
 
 #include "../../include/fsem_lsd.h"
 #include "fsem_build_marker.h"
-#include "fsem_common.h"
+#include "fsem_complex.h"
 
 namespace fsem {
 namespace lsd {
@@ -90,24 +90,12 @@ __global__ __launch_bounds__(T) void lsd_partial(const float *__restrict__ ref, 
   for (int j = 0; j < C / (4 * T); ++j) {
     const int a = base + 4 * (tid + T * j);
     if (a >= n) continue;
-    float sv[4], hv[4];
-    if (VEC) {  // a % 4 == 0 and a < n: the float4 lies inside the row's ceil4(length) floats
-      const float4 s4 = *reinterpret_cast<const float4 *>(srow + a);
-      const float4 h4 = *reinterpret_cast<const float4 *>(hrow + a);
-      sv[0] = s4.x, sv[1] = s4.y, sv[2] = s4.z, sv[3] = s4.w;
-      hv[0] = h4.x, hv[1] = h4.y, hv[2] = h4.z, hv[3] = h4.w;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bool in = a + e < n;
-        sv[e] = in ? srow[a + e] : 0.f;
-        hv[e] = in ? hrow[a + e] : 0.f;
-      }
-    }
+    float sv[4], hv[4];  // zeros from sample n on
+    load4<VEC>(srow, a, n, sv);
+    load4<VEC>(hrow, a, n, hv);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const bool in = a + e < n;
-      const double sd = in ? sv[e] : 0.f, hd = in ? hv[e] : 0.f;
+      const double sd = sv[e], hd = hv[e];
       sh = fma(sd, hd, sh);
       hh = fma(hd, hd, hh);
     }
@@ -145,37 +133,8 @@ __global__ __launch_bounds__(ST) void lsd_scale(const Part *__restrict__ part, i
 }
 
 // ---- one-wave 512-point complex transform in double: fsem_fft.h's radix-8 Stockham scheme (the
-// same stages, exchange pattern and swizzle) on complex doubles, twiddles read from an LDS table.
-__device__ __forceinline__ cd cadd(cd a, cd b) { return {a.r + b.r, a.i + b.i}; }
-__device__ __forceinline__ cd csub(cd a, cd b) { return {a.r - b.r, a.i - b.i}; }
-__device__ __forceinline__ cd cmul(cd a, cd b) { return {fma(a.r, b.r, -a.i * b.i), fma(a.r, b.i, a.i * b.r)}; }
-__device__ __forceinline__ cd mul_mi(cd a) { return {a.i, -a.r}; }  // a * (-i)
-
-// In-register forward DFT of 8 points (radix-2 DIT, W8 = exp(-i pi/4)).
-__device__ __forceinline__ void dft8(cd v[8]) {
-  const double h = 0.70710678118654752440;
-  const cd a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]);
-  const cd a2 = cadd(v[2], v[6]), a3 = mul_mi(csub(v[2], v[6]));
-  const cd a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]);
-  const cd a6 = cadd(v[3], v[7]), a7 = mul_mi(csub(v[3], v[7]));
-  const cd b0 = cadd(a0, a2), b2 = csub(a0, a2), b1 = cadd(a1, a3), b3 = csub(a1, a3);
-  const cd c0 = cadd(a4, a6), c2 = csub(a4, a6), c1 = cadd(a5, a7), c3 = csub(a5, a7);
-  const cd w1c1 = {h * (c1.r + c1.i), h * (c1.i - c1.r)};   // c1 * (1 - i)/sqrt2
-  const cd w3c3 = {h * (c3.i - c3.r), -h * (c3.r + c3.i)};  // c3 * (-1 - i)/sqrt2
-  const cd mic2 = mul_mi(c2);
-  v[0] = cadd(b0, c0);
-  v[4] = csub(b0, c0);
-  v[1] = cadd(b1, w1c1);
-  v[5] = csub(b1, w1c1);
-  v[2] = cadd(b2, mic2);
-  v[6] = csub(b2, mic2);
-  v[3] = cadd(b3, w3c3);
-  v[7] = csub(b3, w3c3);
-}
-
-// Element i of a wave's exchange area is stored at fpad(i) (fsem_fft.h's swizzle).
-__device__ __forceinline__ int fpad(int i) { return i ^ ((i >> 3) & 15); }
-
+// same stages, exchange pattern and swizzle) on complex doubles, twiddles read from an LDS table;
+// the butterflies, the complex arithmetic and the swizzle are fsem_complex.h's.
 // v[r] = z[lane + 64 r] -> v[r] = Z[lane + 64 r].  `buf`: this wave's 512 complex doubles of LDS;
 // `tw`: W^k, k = 0 ... 511, in LDS.
 __device__ __forceinline__ void fft512_wave_d(cd v[8], cd *buf, int lane, const cd *tw) {
@@ -289,15 +248,8 @@ __global__ __launch_bounds__(T) void lsd_frames(const float *__restrict__ ref, c
     for (int r = 0; r < 5; ++r) {
       // M = Z[512 - k] for k = lane + 64 r: lane 64 - lane's v[7 - r]; for lane 0 its own v[8 - r]
       // (k = 0: Z[0] itself).  r = 4 is bin 256, kept in lane 0 only.
-      double mr, mi;
-      if (r < 4) {
-        mr = __shfl(v[7 - r].r, plane, 64);
-        mi = __shfl(v[7 - r].i, plane, 64);
-      }
-      if (r == 4 || lane == 0) {
-        mr = v[(8 - r) & 7].r;
-        mi = v[(8 - r) & 7].i;
-      }
+      const cd m = r < 4 ? mirror_bin(v, r, lane, plane) : v[4];
+      const double mr = m.r, mi = m.i;
       // S = (Z + conj M) / 2, H = (Z - conj M) / (2 i)
       const double sr = v[r].r + mr, si = v[r].i - mi, hr = v[r].i + mi, hi = v[r].r - mr;
       const double S2 = s_zero ? 0.0 : 0.25 * fma(sr, sr, si * si);

@@ -183,12 +183,7 @@ __device__ __forceinline__ Item make_item(int64_t item, int nseg, int64_t B, int
 // latency, and the prefetch registers cost spills and scheduling.
 __device__ __forceinline__ void load_tile_lds(const Item &it, int tid, float *tile) {
   const int64_t L = it.L;
-  const uint64_t base = reinterpret_cast<uint64_t>(it.xrow);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-  const uint32_t nbytes = __builtin_amdgcn_readfirstlane((uint32_t)(((L + 3) & ~(int64_t)3) * 4));
-  void *p = reinterpret_cast<void *>(((uint64_t)hi << 32) | lo);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(p, 0, nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = row_rsrc(it.xrow, (uint32_t)(((L + 3) & ~(int64_t)3) * 4));
   const int t0 = (int)it.tstart;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 #pragma unroll
@@ -912,22 +907,7 @@ __global__ void __launch_bounds__(PT, 2)
       for (int r = 0; r < 12; ++r) o[r] = fra[lane + 64 * r];
     };
     auto power_split = [&](const cf v[8], float *qa, float *qb) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float mr = __shfl(v[7 - r].r, plane, 64);
-        float mi = __shfl(v[7 - r].i, plane, 64);
-        if (lane == 0) {
-          mr = v[(8 - r) & 7].r;
-          mi = v[(8 - r) & 7].i;
-        }
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        const f2v z = {v[r].r, v[r].i}, m = {mr, mi};
-        const f2v sm = z + m;
-        const f2v df = z.yx - m.yx;
-        const f2v pp = __builtin_elementwise_fma(sm, sm, df * df);
-        qa[r] = pp.x;
-        qb[r] = pp.y;
-      }
+      pair_powers(v, lane, plane, qa, qb);
       if (lane == 0) {
         qa[0] = 0.f;
         qb[0] = 0.f;

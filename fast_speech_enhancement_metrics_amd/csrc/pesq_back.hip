@@ -44,19 +44,9 @@ __global__ void __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(4)
   const float *__restrict__ bc = bark + b * NBARK * fld;
   const float *__restrict__ bn = bark + (b + B) * NBARK * fld;
   // band rows by raw buffer loads (voffset = 4 * (k * fld + frame))
-  auto rsrc = [](const float *p, int64_t n) {
-    const uint64_t base = reinterpret_cast<uint64_t>(p);
-    // uint32_t: readfirstlane returns int, which would sign-extend into the high word
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    void *q = reinterpret_cast<void *>(((uint64_t)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(q, 0, (int)(n * 4), 0x00020000);
-  };
-  const __amdgpu_buffer_rsrc_t rcl = rsrc(bc, NBARK * fld), rdn = rsrc(bn, NBARK * fld);
+  const __amdgpu_buffer_rsrc_t rcl = row_rsrc(bc, (uint32_t)(NBARK * fld * 4));
+  const __amdgpu_buffer_rsrc_t rdn = row_rsrc(bn, (uint32_t)(NBARK * fld * 4));
   const int fstride = 4 * (int)fld;  // one signal's bands span < 2^29 floats
-  auto ld = [](__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-  };
   // scratch row of this utterance (stride 4 * Fcap): sym [0, F), asym [F, 2F), and with several
   // waves the keep flags from 2 Fcap on (one word per frame, written and read back by one lane)
   float *__restrict__ sym = scratch + b * (int64_t)Fcap * 4;
@@ -100,9 +90,7 @@ __global__ void __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(4)
     pwc = power[b];
     pwn = power[b + B];
   }
-  const float pc = pwc / (float)(L + 5120) / 1.04684f;
-  const float pn = pwn / (float)(L + 5120) / 1.04684f;
-  const float sc = 1e7f / pc, sn = 1e7f / pn;
+  const float sc = level_scale(pwc, L), sn = level_scale(pwn, L);
   const int *__restrict__ exc = pexp ? pexp + b * (int64_t)nseg : nullptr;
   const int *__restrict__ exn = pexp ? pexp + (b + B) * (int64_t)nseg : nullptr;
   // the level scale of frame f (per lane: frames of one chunk may lie in two segments)
@@ -135,7 +123,7 @@ __global__ void __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(4)
     const float scf = scale_at(shc, exc, eC, sc, fi);
 #pragma unroll
     for (int k = 0; k < NBARK; ++k) {
-      const float cl = ld(rcl, 4 * fi + k * fs, 0) * scf;
+      const float cl = buffer_f32(rcl, 4 * fi + k * fs) * scf;
       aud[k] = (cl > kThresh[k] * 100.f) ? cl : 0.f;
       a += aud[k];
     }
@@ -181,7 +169,7 @@ __global__ void __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(4)
     const float snf = scale_at(shn, exn, eN, sn, fi);
 #pragma unroll
     for (int k = 0; k < NBARK; ++k) {
-      const float n = ld(rdn, 4 * fi + k * fs, 0) * snf;
+      const float n = buffer_f32(rdn, 4 * fi + k * fs) * snf;
       acc[k] += (keep && n > kThresh[k] * 100.f) ? n : 0.f;
     }
   }
@@ -219,8 +207,8 @@ __global__ void __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(4)
     const float scf = scale_at(shc, exc, eC, sc, fi), snf = scale_at(shn, exn, eN, sn, fi);
 #pragma unroll
     for (int k = 0; k < NBARK; ++k) {
-      ec[k] = ratio_s[k] * (ld(rcl, 4 * fi + k * fs, 0) * scf);
-      ns[k] = ld(rdn, 4 * fi + k * fs, 0) * snf;
+      ec[k] = ratio_s[k] * (buffer_f32(rcl, 4 * fi + k * fs) * scf);
+      ns[k] = buffer_f32(rdn, 4 * fi + k * fs) * snf;
       ac += (ec[k] > kThresh[k]) ? ec[k] : 0.f;
       an += (ns[k] > kThresh[k]) ? ns[k] : 0.f;
     }
@@ -235,17 +223,11 @@ __global__ void __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(4)
     float s2 = 0.f, as = 0.f;
 #pragma unroll
     for (int k = 0; k < NBARK; ++k) {
-      const float en = r * ns[k];
-      const float lc = loud(ec[k], k), ln = loud(en, k);
-      float d = ln - lc;
-      const float dz = 0.25f * fminf(lc, ln);
-      d = copysignf(fmaxf(fabsf(d) - dz, 0.f), d);
       if (k >= 1) {
-        const float wd = kWidthBark[k] * d;
+        const float en = r * ns[k];
+        const float wd = band_terms(ec[k], en, k).wd;
         s2 = fmaf(wd, wd, s2);
-        float am = pow_pos((en + 50.f) * __builtin_amdgcn_rcpf(ec[k] + 50.f), 1.2f);  // ~1 ulp rcp
-        am = (am < 3.f) ? 0.f : fminf(am, 12.f);
-        as += fabsf(wd * am);
+        as += fabsf(wd * asymmetry_factor(asymmetry_raw(ec[k], en)));
       }
     }
     const float sy = fmaxf(sqrt_tw * sqrtf(s2), 1e-20f);
@@ -266,14 +248,8 @@ __global__ void __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(4)
   const int nw = (F - 20) / 10 + 1;
   double as_ = 0.0, aa_ = 0.0;
   for (int w = tid; w < nw; w += BT) {
-    double s6 = 0.0, a6 = 0.0;
-    for (int i = 0; i < 20; ++i) {
-      const double x = sym[10 * w + i], y = asym[10 * w + i];
-      const double x2 = x * x, y2 = y * y;
-      s6 += x2 * x2 * x2;
-      a6 += y2 * y2 * y2;
-    }
-    const double ps = pow(s6 / 20.0, 1.0 / 6.0), pa = pow(a6 / 20.0, 1.0 / 6.0);
+    double ps, pa;
+    window_l6(w, [&](int f, double &x, double &y) { x = sym[f], y = asym[f]; }, ps, pa);
     as_ += ps * ps;
     aa_ += pa * pa;
   }
@@ -292,8 +268,7 @@ __global__ void __launch_bounds__(64 * BW) __attribute__((amdgpu_waves_per_eu(4)
       ta += dred[1][w];
     }
     const double ds = sqrt(ts / nw), da = sqrt(ta / nw);
-    double m = 4.5 - 0.1 * ds - 0.0309 * da;              // PESQ.py:240
-    m = 0.999 + 4.0 / (1.0 + exp(-1.3669 * m + 3.8224));  // PESQ.py:243
+    const double m = mos_of(ds, da);
     // a signal with zero (or non-finite) band-pass power: the reference's x * sqrt(1e7 / power)
     // (PESQ.py:100) turns it into NaN samples, which torch's clamp / pow propagate to the score;
     // here the scale multiplies Bark bands whose NaNs the comparisons above would drop

@@ -85,15 +85,9 @@ __device__ __forceinline__ FrameOut frame_pass(const Bands &x, bool valid, const
 #pragma unroll 1
   for (int k = 1; k < NBARK; ++k) {
     const float ec = rho[k] * x.clean(k), en = r * x.den(k);
-    const float lc = loud(ec, k), ln = loud(en, k);
-    float d = ln - lc;
-    const float dz = 0.25f * fminf(lc, ln);
-    d = copysignf(fmaxf(fabsf(d) - dz, 0.f), d);
-    const float wd = kWidthBark[k] * d;
+    const float wd = band_terms(ec, en, k).wd;
     s2 = fmaf(wd, wd, s2);
-    float am = pow_pos((en + 50.f) * __builtin_amdgcn_rcpf(ec + 50.f), 1.2f);
-    am = (am < 3.f) ? 0.f : fminf(am, 12.f);
-    as += fabsf(wd * am);
+    as += fabsf(wd * asymmetry_factor(asymmetry_raw(ec, en)));
   }
   o.s2 = s2;
   o.as = as;
@@ -118,17 +112,12 @@ __device__ __forceinline__ FrameOut frame_pass(const Bands &x, bool valid, const
   for (int k = 1; k < NBARK; ++k) {
     const float c = x.clean(k), ns = x.den(k);
     const float ec = rho[k] * c, en = r * ns;
-    const float lc = loud(ec, k), ln = loud(en, k);
-    const float d0 = ln - lc;
-    const float dz = 0.25f * fminf(lc, ln);
-    const float mag = fabsf(d0) - dz;
-    const bool act = mag > 0.f;
-    const float d = copysignf(fmaxf(mag, 0.f), d0);
+    const BandTerms bt = band_terms(ec, en, k);
+    const float lc = bt.lc, ln = bt.ln, d0 = bt.d0, wd = bt.wd;
+    const bool act = bt.mag > 0.f;
     const float wb = kWidthBark[k];
-    const float wd = wb * d;
-    const float rat = (en + 50.f) * __builtin_amdgcn_rcpf(ec + 50.f);
-    const float am0 = pow_pos(rat, 1.2f);
-    const float am = (am0 < 3.f) ? 0.f : fminf(am0, 12.f);
+    const float am0 = asymmetry_raw(ec, en);
+    const float am = asymmetry_factor(am0);
     const float xx = wd * am;
     const float sg = (xx > 0.f) ? 1.f : ((xx < 0.f) ? -1.f : 0.f);
     const float g_d = 2.f * g_s2 * wb * wd + g_as * sg * wb * am;
@@ -193,9 +182,7 @@ __global__ void __launch_bounds__(GT)
   for (int e = tid; e < 2 * 4 * NBARK; e += GT) (&tot[0][0][0])[e] = 0.f;
   __syncthreads();
   const float pwc = pw_s[0], pwn = pw_s[1];
-  const float pc = pwc / (float)(L + 5120) / 1.04684f;
-  const float pn = pwn / (float)(L + 5120) / 1.04684f;
-  const float sc = 1e7f / pc, sn = 1e7f / pn;
+  const float sc = level_scale(pwc, L), sn = level_scale(pwn, L);
   if (bad_s[0] || bad_s[1] || !__builtin_isfinite(sc) || !__builtin_isfinite(sn)) {  // (uniform)
     if (tid == 0) {
       okv[b] = 0;
@@ -287,14 +274,8 @@ __global__ void __launch_bounds__(GT)
   const int nw = (F - 20) / 10 + 1;
   double as_ = 0.0, aa_ = 0.0;
   for (int w = tid; w < nw; w += GT) {
-    double s6 = 0.0, a6 = 0.0;
-    for (int i = 0; i < 20; ++i) {
-      const double xs = Sv[10 * w + i], y = Av[10 * w + i];
-      const double x2 = xs * xs, y2 = y * y;
-      s6 += x2 * x2 * x2;
-      a6 += y2 * y2 * y2;
-    }
-    const double ps = pow(s6 / 20.0, 1.0 / 6.0), pa = pow(a6 / 20.0, 1.0 / 6.0);
+    double ps, pa;
+    window_l6(w, [&](int f, double &xs, double &y) { xs = Sv[f], y = Av[f]; }, ps, pa);
     as_ += ps * ps;
     aa_ += pa * pa;
     const double ps2 = ps * ps, pa2 = pa * pa;
@@ -312,11 +293,10 @@ __global__ void __launch_bounds__(GT)
     const double ts = ((dred[0][0] + dred[0][1]) + dred[0][2]) + dred[0][3];
     const double ta = ((dred[1][0] + dred[1][1]) + dred[1][2]) + dred[1][3];
     const double ds = sqrt(ts / nw), da = sqrt(ta / nw);
-    const double m = 4.5 - 0.1 * ds - 0.0309 * da;
-    const double e = exp(-1.3669 * m + 3.8224);
-    const double dm = (double)g_mos[b] * 4.0 * 1.3669 * e / ((1.0 + e) * (1.0 + e));  // dL/dm
-    const double gds = (g_sym ? (double)g_sym[b] : 0.0) - 0.1 * dm;
-    const double gda = (g_asym ? (double)g_asym[b] : 0.0) - 0.0309 * dm;
+    const double e = mos_exp(mos_raw(ds, da));
+    const double dm = (double)g_mos[b] * kMosSpan * kMosSlope * e / ((1.0 + e) * (1.0 + e));  // dL/d raw (mos_of)
+    const double gds = (g_sym ? (double)g_sym[b] : 0.0) - kMosSym * dm;
+    const double gda = (g_asym ? (double)g_asym[b] : 0.0) - kMosAsym * dm;
     // d ds / d S_f = S_f^5 / (20 nw ds) sum over the frame's windows of ps^-4
     gd_s[0] = ds > 0.0 ? gds / (20.0 * nw * ds) : 0.0;
     gd_s[1] = da > 0.0 ? gda / (20.0 * nw * da) : 0.0;
@@ -685,35 +665,14 @@ __global__ void __launch_bounds__(GT)
     // Ya = (Z[k] + conj Z[N-k]) / 2, Yb = (Z[k] - conj Z[N-k]) / 2i; G = q Y on bins 1..255;
     // W[k] = conj(Ga + i Gb), W[N-k] = conj(conj Ga + i conj Gb): the transform of W is
     // conj(ga + i gb) with g = Re sum 2 G e^(+i ...), both frames' sample gradients
-    cf wk[4], wm[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float mr = __shfl(v[7 - r].r, plane, 64);
-      float mi = __shfl(v[7 - r].i, plane, 64);
-      if (lane == 0) {
-        mr = v[(8 - r) & 7].r;
-        mi = v[(8 - r) & 7].i;
-      }
-      const float ca = 0.5f * qb[ia][band[r]];
-      const float cb = 0.5f * qb[ia + 1][band[r]];
-      const cf Ga = {ca * (v[r].r + mr), ca * (v[r].i - mi)};
-      const cf Gb = {cb * (v[r].i + mi), -cb * (v[r].r - mr)};
-      wk[r] = {Ga.r - Gb.i, -(Ga.i + Gb.r)};
-      wm[r] = {Ga.r + Gb.i, Ga.i - Gb.r};
-    }
-    wave_lds_fence();
     cf u[8];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      u[r] = wk[r];
-      u[7 - r] = {__shfl(wm[r].r, plane, 64), __shfl(wm[r].i, plane, 64)};
-    }
-    if (lane == 0) {  // bins 64 r mirror to 64 (8 - r); bin 256 lies in no band
-      u[7] = wm[1];
-      u[6] = wm[2];
-      u[5] = wm[3];
-      u[4] = {0.f, 0.f};
-    }
+    pair_grad_fold(
+        v,
+        [&](int r, float &ca, float &cb) {
+          ca = 0.5f * qb[ia][band[r]];
+          cb = 0.5f * qb[ia + 1][band[r]];
+        },
+        lane, plane, u);
     fft512_wave<false>(u, wbuf, lane, tw1, tw2);
 #pragma unroll
     for (int r = 0; r < 8; ++r) {

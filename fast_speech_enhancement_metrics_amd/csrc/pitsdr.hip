@@ -24,7 +24,7 @@
 // the mixture's position, the row capacity, the loads' width or the stream.
 #include <math.h>
 
-#include "fsem_common.h"
+#include "fsem_sdr_rules.h"
 
 namespace fsem {
 namespace pitsdr {
@@ -46,18 +46,6 @@ __host__ __device__ constexpr Off offsets(int S, int E) {
 inline bool rate_ok(int32_t sr) { return sr >= 4000 && sr <= 192000; }
 inline int64_t chunks(int64_t length) { return (length + C - 1) / C; }
 inline int64_t sums_doubles(int S, int E, int64_t length) { return (int64_t)fields(S, E) * (1 + chunks(length)); }
-
-// Four consecutive samples of a row from sample a (a % 4 == 0), zeros from sample `hi` on.
-template <bool VEC>
-__device__ __forceinline__ void load4(const float *__restrict__ row, int a, int hi, float v[4]) {
-  if (VEC && a + 4 <= hi) {
-    const float4 x = *reinterpret_cast<const float4 *>(row + a);
-    v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = a + j < hi ? row[a + j] : 0.f;
-  }
-}
 
 template <int S, int E, bool VEC>
 __global__ __launch_bounds__(T) void pit_partial(const float *__restrict__ src, const float *__restrict__ est,
@@ -119,32 +107,6 @@ __global__ __launch_bounds__(T) void pit_partial(const float *__restrict__ src, 
   if (tid < NT) sums[b * stride + NT * (1 + c) + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-// One pair's scores by sdr_finish's rules, and the (centred, with zero_mean) sums its gradient needs.
-struct Pair {
-  double si, snr, ss, sh, nn;
-};
-__device__ __forceinline__ Pair pair_scores(double ss, double hh, double sh, double dd, double s1, double h1, int n,
-                                            int zero_mean) {
-  Pair p;
-  p.snr = 10.0 * log10(ss / dd);  // 0 / 0: NaN; x / 0: +inf; 0 / x: -inf
-  if (zero_mean) {
-    ss = fmax(ss - s1 * s1 / n, 0.0);
-    sh = sh - s1 * h1 / n;
-    hh = fmax(hh - h1 * h1 / n, 0.0);
-  }
-  p.ss = ss, p.sh = sh, p.nn = 0.0;
-  if (ss == 0.0 || hh == 0.0) {
-    p.si = __builtin_nan("");
-  } else if (dd == 0.0) {
-    p.si = __builtin_inf();
-  } else {
-    const double tt = sh / ss * sh;
-    p.nn = fmax(hh - tt, 0.0);
-    p.si = 10.0 * log10(tt / p.nn);
-  }
-  return p;
-}
-
 // A mixture without a sample, or with a non-finite one (it reaches a sum of squares): NaN everywhere.
 __device__ __forceinline__ bool mixture_bad(const double *__restrict__ tot, int S, int E, int n) {
   const Off o = offsets(S, E);
@@ -177,7 +139,7 @@ __global__ __launch_bounds__(FT) void pit_finish(double *__restrict__ sums, int6
   for (int i = 0; i < S; ++i) {
     for (int e = 0; e < E; ++e) {
       const int k = i * E + e;
-      const Pair p = pair_scores(tot[o.ss + i], tot[o.hh + e], tot[o.sh + k], tot[o.dd + k], tot[o.s1 + i],
+      const PairScores p = pair_scores(tot[o.ss + i], tot[o.hh + e], tot[o.sh + k], tot[o.dd + k], tot[o.s1 + i],
                                  tot[o.h1 + e], n, zero_mean);
       si[i][e] = p.si;
       sn[i][e] = p.snr;
@@ -244,7 +206,7 @@ __global__ __launch_bounds__(T) void pit_grad(const float *__restrict__ src, con
     const bool bad = mixture_bad(tot, S, E, n);
     if (!bad) {
       const double dd = tot[o.dd + tid];
-      const Pair p = pair_scores(tot[o.ss + i], tot[o.hh + e], tot[o.sh + tid], dd, tot[o.s1 + i], tot[o.h1 + e], n,
+      const PairScores p = pair_scores(tot[o.ss + i], tot[o.hh + e], tot[o.sh + tid], dd, tot[o.s1 + i], tot[o.h1 + e], n,
                                  zero_mean);
       const int64_t at = (b * S + i) * E + e;
       if (isfinite(p.si)) {  // (then ss, sh and nn are all non-zero)

@@ -25,7 +25,7 @@
 #include <algorithm>
 #include <math.h>
 
-#include "fsem_common.h"
+#include "fsem_sdr_rules.h"
 
 namespace fsem {
 namespace sdr {
@@ -227,30 +227,15 @@ __global__ __launch_bounds__(FT) void sdr_finish(const Part *__restrict__ part, 
       }
     }
   }
-  double ss = e[0], sh = e[1], hh = e[2];
-  const double dd = e[3];
+  const double ss = e[0], sh = e[1], hh = e[2], dd = e[3];
   if (!isfinite(ss) || !isfinite(hh) || !isfinite(dd) || !isfinite(sh)) {  // a non-finite sample in the row
     si_out[b] = snr_out[b] = seg_out[b] = nanf_;
     return;
   }
-  snr_out[b] = (float)(10.0 * log10(ss / dd));  // 0 / 0: NaN; x / 0: +inf; 0 / x: -inf
+  const PairScores sc = pair_scores(ss, hh, sh, dd, e[4], e[5], n, zero_mean);
+  snr_out[b] = (float)sc.snr;
   seg_out[b] = F > 0 ? (float)(seg / F) : nanf_;
-  if (zero_mean) {
-    ss = fmax(ss - e[4] * e[4] / n, 0.0);
-    sh = sh - e[4] * e[5] / n;
-    hh = fmax(hh - e[5] * e[5] / n, 0.0);
-  }
-  float si;
-  if (ss == 0.0 || hh == 0.0) {
-    si = nanf_;
-  } else if (dd == 0.0) {
-    si = __builtin_inff();
-  } else {
-    const double tt = sh / ss * sh;
-    const double nn = fmax(hh - tt, 0.0);
-    si = (float)(10.0 * log10(tt / nn));
-  }
-  si_out[b] = si;
+  si_out[b] = (float)sc.si;
 }
 
 // Workspace: the squared window, then one record per (row, chunk).

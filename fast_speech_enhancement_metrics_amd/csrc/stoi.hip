@@ -90,12 +90,7 @@ __global__ void __launch_bounds__(256, 2)
     const int64_t n_in = rows.n(b);
     const uint32_t nbytes = (uint32_t)(((n_in + 3) & ~(int64_t)3) * 4);
     const float *row = (sig == 0 ? ref : deg) + b * ld;
-    const uint64_t base = reinterpret_cast<uint64_t>(row);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    void *p = reinterpret_cast<void *>(((uint64_t)hi << 32) | lo);
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(p, 0, __builtin_amdgcn_readfirstlane(nbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = row_rsrc(row, nbytes);
 #pragma unroll
     for (int k = 0; k < XPF; ++k) {
       const int64_t t = i0 + 4 * (tid + 256 * k);
@@ -304,23 +299,12 @@ __global__ void __launch_bounds__(64 * TOB_WAVES)
   const int *kidx = idx + b * nv_ld;
   const float *__restrict__ yc = y10 + (b * 2) * y_ld;
   const float *__restrict__ yd = yc + y_ld;
-  // range-checked raw buffer loads over each row's [0, L10): samples past the row end read as 0
-  // without a branch per load (torchaudio's zero padding of the overlap-added signal)
-  auto row_rsrc = [L10](const float *y) {
-    const uint64_t base = reinterpret_cast<uint64_t>(y);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-    void *p = reinterpret_cast<void *>(((uint64_t)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(p, 0, __builtin_amdgcn_readfirstlane((uint32_t)(L10 * 4)), 0x00020000);
-  };
-  const __amdgpu_buffer_rsrc_t rc = row_rsrc(yc), rd = row_rsrc(yd);
-  auto at = [](__amdgpu_buffer_rsrc_t r, int64_t o) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)(o * 4), 0, 0));
-  };
-  const float w_lo = kHann256s[lane], w_lo2 = kHann256s[lane + 64];
-  const float w_hi = kHann256s[128 + lane], w_hi2 = kHann256s[128 + 64 + lane];
+  // each row's [0, L10) by range-checked loads (sample_at)
+  const __amdgpu_buffer_rsrc_t rc = row_rsrc(yc, (uint32_t)(L10 * 4)), rd = row_rsrc(yd, (uint32_t)(L10 * 4));
+  float win[4];  // STFT window on the 256 centred samples
+  hann_quad(lane, win);
 
-  // overlap-added blocks q = k0+1 .. kend+1:  block_q[t] = w[t] F_{i_q}[t] + w[128+t] F_{i_{q-1}}[128+t]
+  // overlap-added blocks q = k0+1 .. kend+1 (ola_block)
   const int nblk = kend - k0 + 1;
   // every block of the wave in flight at once (one memory latency round): blocks past nblk
   // re-read the last block (clamped kept index) and are not stored
@@ -329,27 +313,18 @@ __global__ void __launch_bounds__(64 * TOB_WAVES)
 #pragma unroll
   for (int u = 0; u < NBW; ++u) {
     const int j = min(wave + TOB_WAVES * u, nblk - 1);
-    const int q = k0 + 1 + j;
-    const int iq = kidx[q], ip = kidx[q - 1];
-    const int64_t a0 = 128LL * iq, a1 = 128LL * ip + 128;
-    g[u][0] = at(rc, a0 + lane);
-    g[u][1] = at(rc, a1 + lane);
-    g[u][2] = at(rc, a0 + 64 + lane);
-    g[u][3] = at(rc, a1 + 64 + lane);
-    g[u][4] = at(rd, a0 + lane);
-    g[u][5] = at(rd, a1 + lane);
-    g[u][6] = at(rd, a0 + 64 + lane);
-    g[u][7] = at(rd, a1 + 64 + lane);
+    ola_taps(rc, kidx, k0 + 1 + j, lane, g[u]);
+    ola_taps(rd, kidx, k0 + 1 + j, lane, g[u] + 4);
   }
 #pragma unroll
   for (int u = 0; u < NBW; ++u) {
     const int j = wave + TOB_WAVES * u;
     if (j < nblk) {  // uniform
       // plain lane-ordered stores (one address VGPR, immediate offsets): no M0 juggling
-      blk[0][j][lane] = w_lo * g[u][0] + w_hi * g[u][1];
-      blk[0][j][64 + lane] = w_lo2 * g[u][2] + w_hi2 * g[u][3];
-      blk[1][j][lane] = w_lo * g[u][4] + w_hi * g[u][5];
-      blk[1][j][64 + lane] = w_lo2 * g[u][6] + w_hi2 * g[u][7];
+      blk[0][j][lane] = ola_block(win, g[u], 0);
+      blk[0][j][64 + lane] = ola_block(win, g[u], 1);
+      blk[1][j][lane] = ola_block(win, g[u] + 4, 0);
+      blk[1][j][64 + lane] = ola_block(win, g[u] + 4, 1);
     }
   }
   lds_stores_done();  // other waves read these blocks
@@ -358,7 +333,6 @@ __global__ void __launch_bounds__(64 * TOB_WAVES)
 
   cf tw1[8], tw2[8];
   fft512_twiddles(lane, tw1, tw2);
-  const float win[4] = {w_lo, w_lo2, w_hi, w_hi2};  // STFT window on the 256 centred samples
   float2 *wbuf = reinterpret_cast<float2 *>(xbuf) + wave * kFftBuf;
   float *pbuf = reinterpret_cast<float *>(wbuf);
   const int plane = (64 - lane) & 63;
@@ -395,21 +369,13 @@ __global__ void __launch_bounds__(64 * TOB_WAVES)
     // exactly Hermitian: ~1e-7 of the other frame's spectrum would leak into it, and the segment
     // normalisation (STOI.py:113-119) would turn that leak into a correlation (an all-zero
     // denoised signal next to non-zero frames would score like noise, not 0).
-    // The same rounding leaks ~1e-7 of the louder frame's spectrum into the quieter one's, so a
-    // frame ~100 dB or more below its neighbour (an onset after silence) would lose its spectrum
-    // to the leak.  Pairs with a gap of 2^7 or more in peak sample are equalised first: frame b
-    // is scaled by 2^sh to frame a's peak exponent (exact in floating point), its power by 2^-2sh
-    // after the FFT (exact again).
-    const uint32_t pk = peak_exponents(v[0].r, v[1].r, v[2].r, v[3].r, v[0].i, v[1].i, v[2].i, v[3].i);
-    const int ea = (int)(pk >> 16), eb = (int)(pk & 0xffffu);
+    int ea, eb;
+    pair_peaks(v, ea, eb);
     const bool a_zero = ea == 0 && !__any(v[0].r != 0.f || v[1].r != 0.f || v[2].r != 0.f || v[3].r != 0.f);
     const bool b_zero = eb == 0 && !__any(v[0].i != 0.f || v[1].i != 0.f || v[2].i != 0.f || v[3].i != 0.f);
-    int sh = (ea > 0 && eb > 0) ? ea - eb : 0;
-    sh = (sh >= 7 || sh <= -7) ? max(-60, min(60, sh)) : 0;
-    if (sh != 0) {  // uniform
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r].i = __builtin_amdgcn_ldexpf(v[r].i, sh);
-    }
+    // Frames far apart in level are equalised first (pair_level_shift): frame b's power is scaled
+    // by 2^-2sh after the FFT.
+    const int sh = pair_level_shift(v, ea, eb);
     // wave-uniform factors, applied to the band envelopes after the square root (powers of two:
     // the same values as scaling every bin's power by 0.25 (x 2^-2sh for frame b's power),
     // short of under/overflow), or 0 for a zero frame.  Scaling after the root keeps the
@@ -419,24 +385,7 @@ __global__ void __launch_bounds__(64 * TOB_WAVES)
     const float b_scale = b_zero ? 0.f : __builtin_amdgcn_ldexpf(0.5f, -sh);
     fft512_wave<true>(v, wbuf, lane, tw1, tw2);  // v[4..7] = 0: the frame's zero-padded half
     float pa[4], pb[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float mr = __shfl(v[7 - r].r, plane, 64);
-      float mi = __shfl(v[7 - r].i, plane, 64);
-      if (lane == 0) {
-        mr = v[(8 - r) & 7].r;
-        mi = v[(8 - r) & 7].i;
-      }
-      // (pa, pb) = (|zr + mr|^2 + (zi - mi)^2, |zi + mi|^2 + (zr - mr)^2) in packed FP32:
-      // the same per-element operations as the scalar form, half the instructions
-      typedef float f2v __attribute__((ext_vector_type(2)));
-      const f2v z = {v[r].r, v[r].i}, m = {mr, mi};
-      const f2v sm = z + m;
-      const f2v df = z.yx - m.yx;  // (zi - mi, zr - mr)
-      const f2v pp = __builtin_elementwise_fma(sm, sm, df * df);
-      pa[r] = pp.x;
-      pb[r] = pp.y;
-    }
+    pair_powers(v, lane, plane, pa, pb);
     // plain lane-ordered stores: one address VGPR for the kernel, immediate offsets (paired
     // ds_write2st64_b32) -- no M0 save / set / hazard nop / restore per store (4 SALU each, 32
     // per transform: the kernel is issue bound, SQ_INSTS_SALU 45 % of its VALU count)

@@ -307,25 +307,16 @@ __global__ void __launch_bounds__(64 * TGW)
   const int kend = min(k0 + TF, T);
   const int *kidx = idx + b * nv_ld;
   const float *__restrict__ yd = y10 + (b * 2 + 1) * y_ld;
-  // range-checked loads over the row's [0, L10), as stoi_tob
-  const uint64_t base = reinterpret_cast<uint64_t>(yd);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<void *>(((uint64_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane((uint32_t)(L10 * 4)),
-      0x00020000);
-  auto at = [](__amdgpu_buffer_rsrc_t r, int64_t o) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)(o * 4), 0, 0));
-  };
-  const float w_lo = kHann256s[lane], w_lo2 = kHann256s[lane + 64];
-  const float w_hi = kHann256s[128 + lane], w_hi2 = kHann256s[128 + 64 + lane];
-  // overlap-added blocks q = k0 + 1 .. kend + 1 of the denoised row, as stoi_tob builds them
+  const __amdgpu_buffer_rsrc_t rd = row_rsrc(yd, (uint32_t)(L10 * 4));  // the row's [0, L10) (sample_at)
+  float win[4];
+  hann_quad(lane, win);
+  // overlap-added blocks q = k0 + 1 .. kend + 1 of the denoised row
   const int nblk = kend - k0 + 1;
   for (int j = wave; j < nblk; j += TGW) {
-    const int q = k0 + 1 + j;
-    const int64_t a0 = 128LL * kidx[q], a1 = 128LL * kidx[q - 1] + 128;
-    blk[j][lane] = w_lo * at(rd, a0 + lane) + w_hi * at(rd, a1 + lane);
-    blk[j][64 + lane] = w_lo2 * at(rd, a0 + 64 + lane) + w_hi2 * at(rd, a1 + 64 + lane);
+    float g[4];
+    ola_taps(rd, kidx, k0 + 1 + j, lane, g);
+    blk[j][lane] = ola_block(win, g, 0);
+    blk[j][64 + lane] = ola_block(win, g, 1);
   }
   // gY / Y per (frame, band): a frame's derivative is the sum of the at most two tiles it lies in
   const int nwb = (S + GW - 1) / GW;
@@ -348,7 +339,6 @@ __global__ void __launch_bounds__(64 * TGW)
 
   cf tw1[8], tw2[8];
   fft512_twiddles(lane, tw1, tw2);
-  const float win[4] = {w_lo, w_lo2, w_hi, w_hi2};
   float2 *wbuf = reinterpret_cast<float2 *>(xbuf) + wave * kFftBuf;
   const int plane = (64 - lane) & 63;
   int band[4];
@@ -374,50 +364,22 @@ __global__ void __launch_bounds__(64 * TGW)
     }
 #pragma unroll
     for (int r = 4; r < 8; ++r) v[r] = {0.f, 0.f};
-    // frames far apart in level are equalised by a power of two first (stoi_tob: the shared
-    // transform's rounding leaks ~1e-7 of the louder frame into the quieter one's spectrum)
-    const uint32_t pk = peak_exponents(v[0].r, v[1].r, v[2].r, v[3].r, v[0].i, v[1].i, v[2].i, v[3].i);
-    const int ea = (int)(pk >> 16), eb = (int)(pk & 0xffffu);
-    int sh = (ea > 0 && eb > 0) ? ea - eb : 0;
-    sh = (sh >= 7 || sh <= -7) ? max(-60, min(60, sh)) : 0;
-    if (sh != 0) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r].i = __builtin_amdgcn_ldexpf(v[r].i, sh);
-    }
-    const float b_scale = __builtin_amdgcn_ldexpf(0.25f, -sh);
+    // frames far apart in level are equalised first, exactly as the forward does (pair_level_shift)
+    int ea, eb;
+    pair_peaks(v, ea, eb);
+    const float b_scale = __builtin_amdgcn_ldexpf(0.25f, -pair_level_shift(v, ea, eb));
     fft512_wave<true>(v, wbuf, lane, tw1, tw2);
     // Za = (Z[k] + conj Z[N-k]) / 2, Zb = (Z[k] - conj Z[N-k]) / 2i; G = (gY / Y) Z per frame;
     // W[k] = conj(Ga + i Gb) / 2 and W[N-k] = conj(conj Ga + i conj Gb) / 2: the transform of W is the
     // conjugate of ga + i gb, the derivatives with respect to both frames' samples
-    cf wk[4], wm[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float mr = __shfl(v[7 - r].r, plane, 64);
-      float mi = __shfl(v[7 - r].i, plane, 64);
-      if (lane == 0) {
-        mr = v[(8 - r) & 7].r;
-        mi = v[(8 - r) & 7].i;
-      }
-      const float ca = 0.25f * qb[ja][band[r]];
-      const float cb = has_b ? b_scale * qb[ja + 1][band[r]] : 0.f;
-      const cf Ga = {ca * (v[r].r + mr), ca * (v[r].i - mi)};
-      const cf Gb = {cb * (v[r].i + mi), -cb * (v[r].r - mr)};
-      wk[r] = {Ga.r - Gb.i, -(Ga.i + Gb.r)};
-      wm[r] = {Ga.r + Gb.i, Ga.i - Gb.r};
-    }
-    wave_lds_fence();
     cf u[8];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      u[r] = wk[r];
-      u[7 - r] = {__shfl(wm[r].r, plane, 64), __shfl(wm[r].i, plane, 64)};
-    }
-    if (lane == 0) {  // bins 64 r mirror to 64 (8 - r); bin 256 lies in no band
-      u[7] = wm[1];
-      u[6] = wm[2];
-      u[5] = wm[3];
-      u[4] = {0.f, 0.f};
-    }
+    pair_grad_fold(
+        v,
+        [&](int r, float &ca, float &cb) {
+          ca = 0.25f * qb[ja][band[r]];
+          cb = has_b ? b_scale * qb[ja + 1][band[r]] : 0.f;
+        },
+        lane, plane, u);
     fft512_wave<false>(u, wbuf, lane, tw1, tw2);
     float *fa = gf + ((int64_t)b * tmax + k0 + ja) * 256;
 #pragma unroll

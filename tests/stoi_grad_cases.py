@@ -28,6 +28,10 @@ SETS = (("16k", 16000, 16000), ("10k", 10000, 9000), ("8k", 8000, 8000), ("48k",
 LONG = ("long10k", 10000, 50000)   # one row with more than 256 segments (two forward segment blocks, five waves)
 RAGGED_LENGTHS = [16000, 12001, 9000, 4000]
 ODD_LENGTH = 16001
+# 10 kHz rows of 40 VAD frames whose estimate drops to 2^-20 of its level at sample GAP_STEP: the STFT frame pair
+# across the step lies 20 peak exponents apart, so both stoi_tob and stoi_tob_grad equalise it (pair_level_shift;
+# no other case has a kept frame pair 7 or more exponents apart)
+GAP_LENGTH, GAP_STEP = 5248, 128 * 22
 BAR_FACTOR = 32.0
 UPSTREAMS = ((1.0, 0.0), (0.0, 1.0))
 RTOL_CPU = 1e-9      # CPU mode against the reference, of the row's largest gradient
@@ -49,6 +53,11 @@ def rows(name: str):
     if name == "odd":
         c, n, _ = synthetic.speech_like_pairs(4, ODD_LENGTH, 16000, seed=SEED)
         return c, n, 16000
+    if name == "gap":
+        c, n, _ = synthetic.speech_like_pairs(4, GAP_LENGTH, 10000, seed=SEED)
+        n = n.clone()
+        n[:, GAP_STEP:] *= 2.0 ** -20
+        return c, n, 10000
     if name == "zero":  # the 16 kHz set with an all-zero estimate in row 1
         c, n, sr = rows("16k")
         n = n.clone()

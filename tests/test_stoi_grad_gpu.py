@@ -1,6 +1,7 @@
 """STOI with gradients on the HIP engine (csrc/stoi_grad.hip) against the float64 reference of
 tests/stoi_grad_cases.py: the forward bitwise against ``STOI.scores``, the gradient at every rate path (10 kHz
-direct, 16 kHz, 8 and 48 kHz generic) for the incoming gradients (1, 0), (0, 1) and a random pair, the
+direct, 16 kHz, 8 and 48 kHz generic) for the incoming gradients (1, 0), (0, 1) and a random pair, also on rows
+with a frame pair 20 peak exponents apart (the level equalisation the backward shares with the forward), the
 conventions (rows without a gradient, zero envelopes, ragged rows), reproducibility, row layouts, a few
 optimiser steps and one direct call of the C entries.
 
@@ -63,7 +64,7 @@ def test_forward_is_scores_bitwise(name):
 
 
 @pytest.mark.parametrize("upstream", [(1.0, 0.0), (0.0, 1.0), "random"], ids=["stoi", "estoi", "random"])
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + ["gap"])   # "gap": a frame pair that the backward has to level-equalise
 def test_gradient_against_the_reference(name, upstream):
     want = gc.expected(name)
     s, e, grad, g = engine_set(name, upstream)
