@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+from . import contract
+
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 HEADER = os.path.join(REPO, "include", "fsem.h")
 
@@ -20,9 +22,7 @@ def declared_functions():
 
 @pytest.fixture(scope="module")
 def lib():
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 def test_library_exports_every_declared_symbol(lib):

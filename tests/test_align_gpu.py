@@ -10,14 +10,14 @@ import pytest
 import torch
 
 from oracle import align_oracle as A
+from tests import contract
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
+    return contract.device()
 
 
 def _delayed(batch, length, seed, span):

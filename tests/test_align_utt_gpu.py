@@ -14,14 +14,14 @@ import torch
 from fast_speech_enhancement_metrics_amd.alignment import time_align, time_align_segments
 from oracle import align_oracle as A
 from tests import align_cases as AC
+from tests import contract
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
+    return contract.device()
 
 
 def _check(res, want, B):

@@ -17,14 +17,14 @@ from fast_speech_enhancement_metrics_amd.alignment import realign_bad_intervals,
 from oracle import align_oracle as A
 from oracle import pesq_oracle as po
 from tests import align_cases as AC
+from tests import contract
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
+    return contract.device()
 
 
 @pytest.fixture(scope="module")

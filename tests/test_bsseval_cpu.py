@@ -5,8 +5,6 @@ corner against BSSSDR and the reference's goldens, the assignment, SDRi, the NaN
 API."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import torch
 
 from fast_speech_enhancement_metrics_amd import BSSEval, _build, _cpu, _native
 
+from . import contract
 from . import bsseval_cases as bc
 from . import bsssdr_cases as sc
 
@@ -23,8 +22,7 @@ ENTRIES = ("fsem_bsseval_max_sources", "fsem_bsseval_corr_doubles", "fsem_bsseva
 
 @pytest.fixture(scope="module")
 def lib():
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 @pytest.fixture(scope="module")
@@ -33,17 +31,8 @@ def metric():
 
 
 def test_entries_are_declared_exported_and_bound(lib):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "fsem.h")).read(), flags=re.S)
-    out = subprocess.run(["nm", "-D", "--defined-only", _build.LIB], capture_output=True, text=True, check=True).stdout
-    exported = {n for n in re.findall(r" T (fsem_[a-z0-9_]+)", out) if n.startswith("fsem_bsseval_")}
-    declared = set(re.findall(r"\b(fsem_bsseval_[a-z0-9_]+)\s*\(", header))
-    bound = {n for n in _native.SIGNATURES if n.startswith("fsem_bsseval_")}
-    assert exported == declared == bound == set(ENTRIES)
-    for name in ENTRIES:
-        fn = getattr(lib, name)
-        assert fn.restype is _native.SIGNATURES[name][0] and fn.argtypes == _native.SIGNATURES[name][1]
-        assert ctypes.c_size_t not in _native.SIGNATURES[name][1] and not name.endswith("_workspace_bytes")
-    assert "bsseval.hip" in _build.SOURCES and lib.fsem_version() == 11
+    contract.entries_are_declared_exported_and_bound(lib, "fsem_bsseval_", ENTRIES)
+    assert "bsseval.hip" in _build.SOURCES
 
 
 def test_queries(lib):
@@ -59,32 +48,18 @@ def test_queries(lib):
 def test_abi_refuses_before_launch(lib):
     # (no GPU here: a launch would come back as FSEM_ELAUNCH; dummy non-null pointers are never read)
     p, null = ctypes.c_void_p(16), None
-    ok = dict(src=p, est=p, batch=3, S=2, E=2, length=8000, ld=8000, lengths=null, norms=p, corr=p, coh=p, coh_all=p)
-
-    def call(**kw):
-        a = {**ok, **kw}
-        return lib.fsem_bsseval_f32(a["src"], a["est"], a["batch"], a["S"], a["E"], a["length"], a["ld"], a["lengths"],
-                                    a["norms"], a["corr"], a["coh"], a["coh_all"], null)
-
-    for name in ("src", "est", "norms", "corr", "coh", "coh_all"):
-        assert call(**{name: null}) == _native.FSEM_EINVAL, name
     big = (1 << 29) + 1
-    for kw in (dict(batch=-1), dict(S=0), dict(S=5), dict(E=0), dict(E=5), dict(length=0), dict(ld=7999),
-               dict(length=big, ld=big)):
-        assert call(**kw) == _native.FSEM_EINVAL, kw
-    assert call(batch=0) == _native.FSEM_OK  # nothing to score, nothing launched
+    EINVAL, OK = _native.FSEM_EINVAL, _native.FSEM_OK
+    call = contract.by_name(lib.fsem_bsseval_f32, "src est batch S E length ld lengths norms corr coh coh_all", null)
+    ok = dict(src=p, est=p, batch=3, S=2, E=2, length=8000, ld=8000, lengths=null, norms=p, corr=p, coh=p, coh_all=p)
+    contract.refusals(call, ok, contract.nulled(EINVAL, "src est norms corr coh coh_all") + contract.each(
+        EINVAL, dict(batch=-1), dict(S=0), dict(S=5), dict(E=0), dict(E=5), dict(length=0), dict(ld=7999),
+        dict(length=big, ld=big)) + contract.each(OK, dict(batch=0)))  # nothing to score, nothing launched
+    scores = contract.by_name(lib.fsem_bsseval_scores_f32, "coh coh_all batch S E crit sdr sir sar perm sdm sim", null)
     oks = dict(coh=p, coh_all=p, batch=3, S=2, E=2, crit=1, sdr=p, sir=p, sar=p, perm=p, sdm=null, sim=null)
-
-    def scores(**kw):
-        a = {**oks, **kw}
-        return lib.fsem_bsseval_scores_f32(a["coh"], a["coh_all"], a["batch"], a["S"], a["E"], a["crit"], a["sdr"],
-                                           a["sir"], a["sar"], a["perm"], a["sdm"], a["sim"], null)
-
-    for name in ("coh", "coh_all", "sdr", "sir", "sar", "perm"):
-        assert scores(**{name: null}) == _native.FSEM_EINVAL, name
-    for kw in (dict(batch=-1), dict(S=0), dict(S=5), dict(E=0), dict(E=5), dict(crit=-1), dict(crit=3), dict(S=1, E=2)):
-        assert scores(**kw) == _native.FSEM_EINVAL, kw
-    assert scores(batch=0) == _native.FSEM_OK and scores(batch=0, sdm=p, sim=p) == _native.FSEM_OK
+    contract.refusals(scores, oks, contract.nulled(EINVAL, "coh coh_all sdr sir sar perm") + contract.each(
+        EINVAL, dict(batch=-1), dict(S=0), dict(S=5), dict(E=0), dict(E=5), dict(crit=-1), dict(crit=3), dict(S=1, E=2))
+        + contract.each(OK, dict(batch=0), dict(batch=0, sdm=p, sim=p)))
 
 
 def test_cases_are_stable():

@@ -11,18 +11,9 @@ from fast_speech_enhancement_metrics_amd import BSSSDR, BSSEval, _cpu, _native
 
 from . import bsseval_cases as bc
 from . import bsssdr_cases as sc
+from .contract import assert_bitwise, on_side_stream
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    t = t.cpu()
-    return t.numpy().view(np.uint32) if t.dtype == torch.float32 else t.numpy()
-
-
-def assert_bitwise(got, want, what=""):
-    for g, w in zip(got, want):
-        np.testing.assert_array_equal(_bits(g), _bits(w), err_msg=what)
 
 
 @pytest.fixture(scope="module")
@@ -124,11 +115,7 @@ def test_batch_position_and_stride_invariance(metric):
     coh, coh_all, _, _ = BSSEval.engine_energies(ws, wh, 1, 2, 2, n, ld, None)
     wide = BSSEval._from_energies(coh, coh_all, "SIR", True)
     assert_bitwise(wide, alone, "a wider row stride")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        again = metric.scores(sg, hg, lengths=lens, return_matrix=True)
-    side.synchronize()
+    again = on_side_stream(lambda: metric.scores(sg, hg, lengths=lens, return_matrix=True))
     assert_bitwise(again, base, "a side stream")
 
 

@@ -2,11 +2,7 @@
 the float64 statement of the definition (tests/bsssdr_cases.py) and the reference's own scores
 (tests/golden/bsssdr_*.npz), the edge semantics, the C-ABI's host-side queries and validation (no
 launch), copying and pickling."""
-import copy
-import ctypes
-import json
 import os
-import pickle
 import warnings
 
 import numpy as np
@@ -14,17 +10,15 @@ import pytest
 import torch
 
 from . import bsssdr_cases as bc
-from .test_workspace_cpu import PAIRS
+from . import contract
+from . import pair_metrics as pm
 
-WS_GOLDEN = os.path.join(bc.GOLDEN, "bsssdr_workspace_bytes.json")
 GOLDEN_FILES = ("bsssdr_16k", "bsssdr_8k", "bsssdr_white")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 @pytest.fixture(scope="module")
@@ -162,15 +156,7 @@ def test_ragged_rows_and_no_samples():
 
 
 def test_nonfinite_row_is_nan_alone():
-    from fast_speech_enhancement_metrics_amd import BSSSDR
-    c, n = bc.white_rows(4, 4000)
-    n2, c2 = n.clone(), c.clone()
-    n2[1, 2000] = float("nan")
-    c2[3, 17] = float("inf")
-    m = BSSSDR(16000)
-    base, got = m.scores(c, n), m.scores(c2, n2)
-    assert torch.isnan(got[[1, 3]]).all()
-    assert torch.equal(got[[0, 2]], base[[0, 2]])
+    pm.nonfinite_row_is_nan_alone("BSSSDR")
 
 
 def test_load_diag_and_fixed_attributes():
@@ -190,18 +176,6 @@ def test_load_diag_and_fixed_attributes():
         m.scores(c, n)
 
 
-def test_copy_and_pickle():
-    from fast_speech_enhancement_metrics_amd import BSSSDR
-    c, n = bc.white_rows(2, 6000)
-    m = BSSSDR(8000, use_gpu=False)
-    want = m(c, n)
-    for m2 in (copy.copy(m), copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
-        assert isinstance(m2, BSSSDR) and m2.sample_rate == 8000 and m2.filter_length == 512
-        assert m2(c, n) == want
-    with pytest.raises(ValueError, match="pass sample_rate"):
-        m.scores(c, n)
-
-
 # ------------------------------------------------------------------ the C-ABI, host side
 def test_abi_geometry(blib):
     assert blib.fsem_bsssdr_filter_length() == 512
@@ -209,50 +183,10 @@ def test_abi_geometry(blib):
     assert C > 0 and C % 2048 == 0 and NC > 0 and NC % 256 == 0
 
 
-def record_workspace(blib) -> list:
-    return [blib.fsem_bsssdr_workspace_bytes(b, l) for b, l in PAIRS]
-
-
-def test_workspace_sizes_equal_the_recorded_ones(blib):
-    """fsem_bsssdr_workspace_bytes is pinned to tests/golden/bsssdr_workspace_bytes.json on
-    test_workspace_cpu's PAIRS (python -m tests.test_bsssdr_cpu re-records)."""
-    with open(WS_GOLDEN) as f:
-        golden = json.load(f)
-    assert golden["pairs"] == [list(p) for p in PAIRS]
-    assert record_workspace(blib) == golden["bsssdr"]
-    assert all(golden["bsssdr"][:-1]) and golden["bsssdr"][-1] == 0  # (last pair: batch 0)
-    assert blib.fsem_bsssdr_workspace_bytes(4, 0) == 0 and blib.fsem_bsssdr_workspace_bytes(1, (1 << 29) + 1) == 0
-
-
 def test_abi_validation_without_launch(blib):
     from fast_speech_enhancement_metrics_amd import _native
-    null, p = None, ctypes.c_void_p(16)
-    f = blib.fsem_bsssdr_f32
-    big = 1 << 40
-    assert f(null, null, 4, 160000, 160000, null, null, null, 0, null) == _native.FSEM_EINVAL
-    assert f(null, p, 4, 160000, 160000, null, p, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, null, 4, 160000, 160000, null, p, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, p, 4, 160000, 160000, null, null, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, p, 0, 160000, 160000, null, p, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, p, 4, 0, 0, null, p, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, p, 4, 160000, 159999, null, p, p, big, null) == _native.FSEM_EINVAL
-    over = (1 << 29) + 4
-    assert f(p, p, 1, over, over, null, p, p, 1 << 62, null) == _native.FSEM_EINVAL
-    size = blib.fsem_bsssdr_workspace_bytes(4, 160000)
-    assert size > 0
-    assert f(p, p, 4, 160000, 160000, null, p, p, 16, null) == _native.FSEM_EWORKSPACE
-    assert f(p, p, 4, 160000, 160000, null, p, p, size - 1, null) == _native.FSEM_EWORKSPACE
-    assert f(p, p, 4, 160000, 160000, null, p, null, big, null) == _native.FSEM_EWORKSPACE
-    g = blib.fsem_bsssdr_load_diag_f32
-    assert g(p, p, 4, 160000, 160000, null, float("nan"), p, p, big, null) == _native.FSEM_EINVAL
-    assert g(p, p, 4, 160000, 160000, null, 0.0, p, p, size - 1, null) == _native.FSEM_EWORKSPACE
-
-
-if __name__ == "__main__":
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    with open(WS_GOLDEN, "w") as f:
-        json.dump({"pairs": [list(p) for p in PAIRS], "bsssdr": record_workspace(_native.load_bsssdr())}, f,
-                  separators=(",", ":"))
-        f.write("\n")
-    print("wrote", WS_GOLDEN)
+    ok, size = pm.one_output_validation(blib, "bsssdr")
+    names = "ref deg batch length ld lengths load out ws ws_bytes"
+    load_diag = contract.by_name(blib.fsem_bsssdr_load_diag_f32, names, None)
+    contract.refusals(load_diag, dict(ok, load=0.0), [(dict(load=float("nan")), _native.FSEM_EINVAL),
+                                                      (dict(ws_bytes=size - 1), _native.FSEM_EWORKSPACE)])

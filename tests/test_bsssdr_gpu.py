@@ -2,7 +2,7 @@
 statement of the definition (tests/bsssdr_cases.py) and the reference's scores: parity, the int16
 scale, ragged rows on each side of every edge of the kernels, row layouts, the resampler, gains,
 delays inside and outside the filter, edge rows, non-finite rows, devices= and the CPU mode."""
-import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -11,16 +11,11 @@ import torch
 from fast_speech_enhancement_metrics_amd import BSSSDR, _native
 
 from . import bsssdr_cases as bc
+from . import contract
+from . import pair_metrics as pm
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def assert_bitwise(got, want, what=""):
-    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
+assert_bitwise = functools.partial(contract.assert_bitwise, names=BSSSDR.KEYS)
 
 
 @pytest.fixture(scope="module")
@@ -108,30 +103,6 @@ def test_rows_shorter_than_the_filter(rows16):
         assert_bitwise(got[b:b + 1], m.scores(cg[b:b + 1, :k], ng[b:b + 1, :k]), f"row {b} (n = {k}) alone")
 
 
-def test_layouts(rows16):
-    c, n, _, _, m = rows16
-    L = 30001
-    want, keep = bc.expected(c[:, :L], n[:, :L])
-    cg, ng = c.cuda(), n.cuda()
-    base = m.scores(cg[:, :L].contiguous(), ng[:, :L].contiguous())  # L % 4 != 0
-    bc.assert_close(base, want, keep, "gpu L=30001")
-    assert_bitwise(m.scores(cg[:, :L], ng[:, :L]), base, "strided view, L % 4 != 0")
-    L4 = 30000
-    v = m.scores(cg[:, :L4], ng[:, :L4])  # ld = 32000 > L, no copy
-    bc.assert_close(v, *bc.expected(c[:, :L4], n[:, :L4]), "gpu strided view")
-    assert_bitwise(m.scores(cg[:, :L4].contiguous(), ng[:, :L4].contiguous()), v, "ld > L")
-    # rows that do not start on 16-byte boundaries
-    wide_c, wide_n = torch.zeros(8, 32003, device="cuda"), torch.zeros(8, 32003, device="cuda")
-    wide_c[:, 1:L4 + 1], wide_n[:, 1:L4 + 1] = cg[:, :L4], ng[:, :L4]
-    assert_bitwise(m.scores(wide_c[:, 1:L4 + 1], wide_n[:, 1:L4 + 1]), v, "unaligned rows")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        s = m.scores(cg[:, :L], ng[:, :L])
-    side.synchronize()
-    assert_bitwise(s, base, "side stream")
-
-
 def test_gains_and_delays(rows16):
     m = rows16[4]
     c, n = bc.delay_rows()
@@ -161,27 +132,12 @@ def test_edge_semantics(rows16):
     assert_bitwise(got[[0, 1, 3, 4]], m.scores(c[[0, 1, 3, 4]].cuda(), n[[0, 1, 3, 4]].cuda()), "beside a NaN row")
 
 
-def test_nonfinite_rows(rows16):
-    c, n, want, keep, m = rows16
-    c2, n2 = c.clone(), n.clone()
-    n2[1, 12345] = float("nan")
-    c2[2, 31999] = float("inf")
-    n2[5, 0] = float("-inf")
-    base, got = m.scores(c.cuda(), n.cuda()), m.scores(c2.cuda(), n2.cuda())
-    assert torch.isnan(got[[1, 2, 5]]).all()
-    assert_bitwise(got[[0, 3, 4, 6, 7]], base[[0, 3, 4, 6, 7]], "finite rows beside non-finite ones")
+def test_nonfinite_rows():
+    pm.nonfinite_rows("BSSSDR")
 
 
-def test_past_grid_limit(rows16):
-    NB = 65537
-    c, n = bc.white_rows(4, 600, seed=23)
-    cg, ng = c.cuda(), n.cuda()
-    m = rows16[4]
-    small = m.scores(cg, ng)
-    reps = -(-NB // 4)
-    big = m.scores(cg.repeat(reps, 1)[:NB].contiguous(), ng.repeat(reps, 1)[:NB].contiguous())
-    np.testing.assert_array_equal(_bits(big), _bits(small)[np.arange(NB) % 4])
-    bc.assert_close(small, *bc.expected(c, n), "gpu 600-sample rows")
+def test_past_grid_limit():
+    pm.past_grid_limit("BSSSDR")
 
 
 def test_load_diag(rows16):
@@ -193,29 +149,10 @@ def test_load_diag(rows16):
     bc.assert_close(m.scores(c.cuda(), n.cuda()), cpu.scores(c, n).double().numpy(), None, "gpu load_diag vs cpu mode")
 
 
-def test_devices_fan_out_and_cpu_mode(rows16):
-    c, n, want, keep, m = rows16
-    m2 = BSSSDR(16000, use_gpu=True, devices=[0, 0])
-    cg, ng = c[:4].cuda(), n[:4].cuda()
-    lens = [32000, 1000, 30001, 600]
-    one = m.scores(cg, ng, lengths=lens)
-    assert_bitwise(m2.scores(cg, ng, lengths=lens), one, "devices=[0, 0] with lengths")
-    cpu = BSSSDR(16000, use_gpu=False).scores(c, n)
-    bc.assert_close(cpu, want, keep, "cpu 16000")
-    bc.assert_close(m.scores(c.cuda(), n.cuda()), cpu.double().numpy(), keep, "gpu vs cpu mode")
+def test_devices_fan_out_and_cpu_mode():
+    pm.devices_fan_out("BSSSDR")
+    pm.cpu_mode_agrees("BSSSDR")
 
 
 def test_abi_refuses_before_launch():
-    lib = _native.load_bsssdr()
-    x = torch.zeros(4, 1000, device="cuda")
-    o = torch.zeros(4, device="cuda")
-    p = ctypes.c_void_p
-    args = (p(x.data_ptr()), p(x.data_ptr()), 4, 1000, 1000, None, p(o.data_ptr()))
-    size = lib.fsem_bsssdr_workspace_bytes(4, 1000)
-    ws = torch.zeros(size, dtype=torch.uint8, device="cuda")
-    assert lib.fsem_bsssdr_f32(*args, p(ws.data_ptr()), 16, None) == _native.FSEM_EWORKSPACE
-    assert lib.fsem_bsssdr_f32(*args, p(ws.data_ptr()), size - 1, None) == _native.FSEM_EWORKSPACE
-    assert lib.fsem_bsssdr_f32(p(x.data_ptr()), p(x.data_ptr()), 4, 1000, 999, None, p(o.data_ptr()),
-                               p(ws.data_ptr()), size, None) == _native.FSEM_EINVAL
-    torch.cuda.synchronize()
-    assert not o.any()  # (nothing ran)
+    pm.refuses_before_launch("BSSSDR")

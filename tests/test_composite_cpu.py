@@ -2,12 +2,8 @@
 against the float64 statement of the definitions (tests/composite_cases.py), the lowest-95 % rule,
 the peak search's quirk, silent and non-finite rows, the drop-in call, the C-ABI's host-side
 validation (no launch), copying and pickling."""
-import copy
 import ctypes
-import json
 import math
-import os
-import pickle
 
 import numpy as np
 import pytest
@@ -17,13 +13,13 @@ from fast_speech_enhancement_metrics_amd import Composite
 
 from . import composite_cases as cc
 from . import sdr_cases as sc
+from . import contract
+from . import pair_metrics as pm
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 @pytest.fixture(scope="module")
@@ -117,15 +113,7 @@ def test_silent_clean_head(zeroed, nan_frames, finite):
 
 
 def test_nonfinite_row_is_nan_alone():
-    c, n = cc.parity_rows(16000)
-    n2, c2 = n.clone(), c.clone()
-    n2[1, 4000] = float("nan")
-    c2[3, 17] = float("inf")
-    m = Composite(16000)
-    base, got = m.scores(c, n), m.scores(c2, n2)
-    for b, g in zip(base, got):
-        assert torch.isnan(g[[1, 3]]).all()
-        assert torch.equal(g[[0, 2]], b[[0, 2]])
+    pm.nonfinite_row_is_nan_alone("Composite")
 
 
 def test_drop_in_call_key_order_and_shape_check():
@@ -153,15 +141,6 @@ def test_drop_in_call_key_order_and_shape_check():
     assert fast_se_metrics.__all__ == ["STOI", "PESQ"]
 
 
-def test_copy_and_pickle():
-    c, n = cc.parity_rows(8000)
-    m = Composite(8000, use_gpu=False)
-    want = m(c, n)
-    for m2 in (copy.copy(m), copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
-        assert isinstance(m2, Composite) and m2.sample_rate == 8000 and m2.lpc_order == 10
-        assert m2(c, n) == want
-
-
 def test_abi_queries(lib, clib):
     for sr in (8000, 16000):
         assert clib.fsem_composite_workspace_bytes(4, 10 * sr, sr) > lib.fsem_pesq_workspace_bytes(4, 160000) > 0
@@ -171,57 +150,24 @@ def test_abi_queries(lib, clib):
     assert lib.fsem_version() == 11  # (libfsem.so is as it was: the composite entries are a library of their own)
 
 
-PAIRS = [(1, 100), (1, 5376), (3, 40077), (7, 160000), (4096, 160000), (70000, 16000), (0, 160000)]
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "composite_workspace_bytes.json")
-
-
-def record_workspace(clib) -> dict:
-    return {str(sr): [clib.fsem_composite_workspace_bytes(b, l, sr) for b, l in PAIRS]
-            for sr in (8000, 16000, 7999, 22050)}
-
-
-def test_workspace_sizes_equal_the_recorded_ones(clib):
-    """fsem_composite_workspace_bytes is pinned to tests/golden/composite_workspace_bytes.json, as
-    libfsem.so's queries are to workspace_bytes.json (python -m tests.test_composite_cpu re-records)."""
-    with open(GOLDEN) as f:
-        golden = json.load(f)
-    assert golden["pairs"] == [list(p) for p in PAIRS]
-    assert record_workspace(clib) == golden["composite"]
-    assert all(golden["composite"]["16000"][:-1]) and all(golden["composite"]["8000"][:-1])  # (last pair: batch 0)
-    assert not any(golden["composite"]["22050"]) and not any(golden["composite"]["7999"])
-
-
 def test_abi_validation_without_launch(clib):
     from fast_speech_enhancement_metrics_amd import _native
     null, p = None, ctypes.c_void_p(16)
-    outs = (p,) * 7
-    f = clib.fsem_composite_f32
-    assert f(null, null, 4, 160000, 160000, null, 16000, *((null,) * 7), null, 0, null) == -1
-    for k in range(7):  # each output pointer
-        assert f(p, p, 4, 160000, 160000, null, 16000, *(outs[:k] + (null,) + outs[k + 1:]), p, 1 << 40, null) == -1
-    assert f(p, p, 0, 160000, 160000, null, 16000, *outs, p, 1 << 40, null) == -1
-    assert f(p, p, 4, 0, 0, null, 16000, *outs, p, 1 << 40, null) == -1
-    assert f(p, p, 4, 160000, 159999, null, 16000, *outs, p, 1 << 40, null) == -1
-    for sr in (3999, 22050, 200000):
-        assert f(p, p, 4, 160000, 160000, null, sr, *outs, p, 1 << 40, null) == _native.FSEM_ERATE
+    outs = [f"o{k}" for k in range(7)]
+    names = "ref deg batch length ld lengths sr " + " ".join(outs) + " ws ws_bytes"
+    call = contract.by_name(clib.fsem_composite_f32, names, null)
+    ok = dict(ref=p, deg=p, batch=4, length=160000, ld=160000, lengths=null, sr=16000, ws=p, ws_bytes=1 << 40,
+              **{o: p for o in outs})
+    big = (1 << 29) + 4
+    half = (1 << 28) + 4  # 8 kHz rows whose 16 kHz copies would pass 2^29 samples
+    contract.refusals(call, ok, contract.nulled(_native.FSEM_EINVAL, " ".join(outs)) + contract.each(  # (each output)
+        _native.FSEM_EINVAL, dict(ref=null, deg=null, ws=null, ws_bytes=0, **{o: null for o in outs}), dict(batch=0),
+        dict(length=0, ld=0), dict(ld=159999), dict(batch=1, length=big, ld=big, ws_bytes=1 << 62),
+        dict(batch=1, length=half, ld=half, sr=8000, ws_bytes=1 << 62))
+        + contract.each(_native.FSEM_ERATE, dict(sr=3999), dict(sr=22050), dict(sr=200000))
+        # the whole-batch form of rows too short for PESQ: refused as fsem_pesq_wb_f32 refuses them
+        + [(dict(length=4000, ld=4000), _native.FSEM_ESHORT)])
     for sr in (8000, 16000):
         size = clib.fsem_composite_workspace_bytes(4, 160000, sr)
-        assert f(p, p, 4, 160000, 160000, null, sr, *outs, p, 16, null) == _native.FSEM_EWORKSPACE
-        assert f(p, p, 4, 160000, 160000, null, sr, *outs, p, size - 1, null) == _native.FSEM_EWORKSPACE
-        assert f(p, p, 4, 160000, 160000, null, sr, *outs, null, 1 << 40, null) == _native.FSEM_EWORKSPACE
-    # the whole-batch form of rows too short for PESQ: refused as fsem_pesq_wb_f32 refuses them
-    assert f(p, p, 4, 4000, 4000, null, 16000, *outs, p, 1 << 40, null) == _native.FSEM_ESHORT
-    big = (1 << 29) + 4
-    assert f(p, p, 1, big, big, null, 16000, *outs, p, 1 << 62, null) == -1
-    half = (1 << 28) + 4  # 8 kHz rows whose 16 kHz copies would pass 2^29 samples
-    assert f(p, p, 1, half, half, null, 8000, *outs, p, 1 << 62, null) == -1
-
-
-if __name__ == "__main__":
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    with open(GOLDEN, "w") as f:
-        json.dump({"pairs": [list(p) for p in PAIRS], "composite": record_workspace(_native.load_composite())}, f,
-                  separators=(",", ":"))
-        f.write("\n")
-    print("wrote", GOLDEN)
+        contract.refusals(call, dict(ok, sr=sr), contract.each(_native.FSEM_EWORKSPACE, dict(ws_bytes=16),
+                                                               dict(ws_bytes=size - 1), dict(ws=null)))

@@ -2,7 +2,7 @@
 (csrc/composite.hip) against the float64 statement of the definitions (tests/composite_cases.py):
 parity at both rates, frame and chunk edges, long rows through the radix select, silent clean
 frames, row layouts, streams, non-finite rows, devices= and the CPU mode."""
-import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -12,17 +12,11 @@ from fast_speech_enhancement_metrics_amd import PESQ, Composite, _native
 
 from . import composite_cases as cc
 from . import sdr_cases as sc
+from . import contract
+from . import pair_metrics as pm
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(ts):
-    return [t.cpu().numpy().view(np.uint32) for t in ts]
-
-
-def assert_bitwise(got, want, what=""):
-    for name, g, w in zip(Composite.KEYS, _bits(got), _bits(want)):
-        np.testing.assert_array_equal(g, w, err_msg=f"{what} {name}")
+assert_bitwise = functools.partial(contract.assert_bitwise, names=Composite.KEYS)
 
 
 def assert_pesq_is_the_class(got, c, n, sr, lengths=None, what=""):
@@ -110,83 +104,13 @@ def test_silent_clean_head(rows, zeroed_ms):
     cc.assert_scores(got, c, n, sr, what=f"gpu silent head {sr} {zeroed_ms} ms", want=want)
 
 
-def test_layouts(rows):
-    sr, c, n, _, m = rows
-    L = c.shape[1] - 3  # L % 4 != 0
-    assert L % 4
-    cg, ng = c.cuda(), n.cuda()
-    base = m.scores(cg[:, :L].contiguous(), ng[:, :L].contiguous())
-    want = cc.assert_scores(base, c[:, :L], n[:, :L], sr, what=f"gpu {sr} L % 4 != 0")
-    cc.assert_scores(m.scores(cg[:, :L], ng[:, :L]), c[:, :L], n[:, :L], sr, what="gpu strided view, L % 4 != 0",
-                     want=want)
-    L4 = c.shape[1] - 400
-    v = m.scores(cg[:, :L4], ng[:, :L4])  # ld > L, no copy
-    cc.assert_scores(v, c[:, :L4], n[:, :L4], sr, what="gpu strided view")
-    # rows that do not start on 16-byte boundaries
-    wide_c = torch.zeros(4, c.shape[1] + 3, device="cuda")
-    wide_n = torch.zeros(4, c.shape[1] + 3, device="cuda")
-    wide_c[:, 1:L4 + 1], wide_n[:, 1:L4 + 1] = cg[:, :L4], ng[:, :L4]
-    assert_bitwise(m.scores(wide_c[:, 1:L4 + 1], wide_n[:, 1:L4 + 1]), v, "unaligned rows")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        s = m.scores(cg[:, :L], ng[:, :L])
-    side.synchronize()
-    assert_bitwise(s, base, "side stream")
-
-
 def test_nonfinite_rows(rows):
-    sr, c, n, _, m = rows
-    c2, n2 = c.clone(), n.clone()
-    n2[1, 5000] = float("nan")
-    c2[2, c.shape[1] - 1] = float("inf")
-    base, got = m.scores(c.cuda(), n.cuda()), m.scores(c2.cuda(), n2.cuda())
-    for g in got:
-        assert torch.isnan(g[[1, 2]]).all()
-    assert_bitwise([g[[0, 3]] for g in got], [b[[0, 3]] for b in base], "finite rows beside non-finite ones")
-
-
-def test_devices_fan_out_and_drop_in(rows):
-    sr, c, n, _, m = rows
-    m2 = Composite(sr, use_gpu=True, devices=[0, 0])
-    cg, ng = c.cuda(), n.cuda()
-    assert_bitwise(m2.scores(cg, ng), m.scores(cg, ng), "devices=[0, 0]")
-    lens = [c.shape[1], 3000, c.shape[1] - 1, 479]
-    one = m.scores(cg, ng, lengths=lens)
-    assert_bitwise(m2.scores(cg, ng, lengths=lens), one, "devices=[0, 0] with lengths")
-    host = [v.cpu().numpy() for v in one]
-    for metric in (m, m2):
-        res = metric(cg, ng, lengths=lens)
-        assert [tuple(r) for r in res] == [Composite.KEYS] * 4
-        for b, r in enumerate(res):
-            for k, key in enumerate(Composite.KEYS):
-                np.testing.assert_array_equal(np.float32(r[key]), host[k][b])
-    # lists of utterances
-    res = m([c[b, :k].cuda() for b, k in enumerate(lens)], [n[b, :k].cuda() for b, k in enumerate(lens)])
-    for b, r in enumerate(res):
-        for k, key in enumerate(Composite.KEYS):
-            np.testing.assert_array_equal(np.float32(r[key]), host[k][b])
+    pm.nonfinite_rows(f"Composite-{rows[0]}")
 
 
 def test_cpu_mode_agrees(rows):
-    sr, c, n, want, m = rows
-    cpu = cc.to_np(Composite(sr, use_gpu=False).scores(c, n))
-    gpu = cc.to_np(m.scores(c.cuda(), n.cuda()))
-    for name, k, atol in (("LLR", 4, cc.ATOL_LLR), ("WSS", 5, cc.ATOL_WSS), ("SegSNR", 6, sc.ATOL_SEG)):
-        err = float(np.abs(cpu[k] - gpu[k]).max())
-        print(f"gpu vs cpu mode {sr} {name}: worst difference {err:.3e}")
-        assert err <= atol, (name, cpu[k], gpu[k])
+    pm.cpu_mode_agrees(f"Composite-{rows[0]}")
 
 
 def test_abi_refuses_before_launch():
-    lib = _native.load_composite()
-    x = torch.zeros(4, 8000, device="cuda")
-    o = torch.zeros(7, 4, device="cuda")
-    p = ctypes.c_void_p
-    args = (p(x.data_ptr()), p(x.data_ptr()), 4, 8000, 8000, None)
-    outs = tuple(p(o[k].data_ptr()) for k in range(7))
-    for sr in (3999, 22050, 200000):
-        assert lib.fsem_composite_f32(*args, sr, *outs, p(x.data_ptr()), 1 << 20, None) == _native.FSEM_ERATE
-    assert lib.fsem_composite_f32(*args, 16000, *outs, p(x.data_ptr()), 16, None) == _native.FSEM_EWORKSPACE
-    torch.cuda.synchronize()
-    assert (o == 0).all()
+    pm.refuses_before_launch("Composite")

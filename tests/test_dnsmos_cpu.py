@@ -3,7 +3,6 @@ file, the segment rule, the CPU mode against the reference's float32 results (te
 the interface (clean=None, shape check, 1-D input, lists and lengths=, the alias path, the weights
 lookup) and the NaN rows."""
 import ctypes
-import json
 import os
 
 import numpy as np
@@ -12,10 +11,8 @@ import torch
 
 from fast_speech_enhancement_metrics_amd import DNSMOS, _cpu
 
+from . import contract
 from . import dnsmos_cases as dc
-from .test_workspace_cpu import PAIRS
-
-WS_GOLDEN = os.path.join(dc.GOLDEN, "dnsmos_workspace_bytes.json")
 
 
 @pytest.fixture(scope="module")
@@ -32,27 +29,6 @@ def metric():
 
 
 # ------------------------------------------------------------------ library and fixtures
-def record_workspace(dlib) -> dict:
-    return {"dnsmos": [dlib.fsem_dnsmos_workspace_bytes(b, l) for b, l in PAIRS],
-            "min": dlib.fsem_dnsmos_min_workspace_bytes(), "weights": dlib.fsem_dnsmos_weights_bytes()}
-
-
-def test_workspace_sizes_equal_the_recorded_ones(dlib):
-    """Pinned to tests/golden/dnsmos_workspace_bytes.json on test_workspace_cpu's PAIRS
-    (python -m tests.test_dnsmos_cpu re-records)."""
-    with open(WS_GOLDEN) as f:
-        golden = json.load(f)
-    assert golden["pairs"] == [list(p) for p in PAIRS]
-    got = record_workspace(dlib)
-    assert got == {k: golden[k] for k in got}
-    assert all(golden["dnsmos"][:-1]) and golden["dnsmos"][-1] == 0  # (last pair: batch 0)
-    # the recommended size stops growing at the cap on segments per pass
-    from fast_speech_enhancement_metrics_amd import _native
-    assert dlib.fsem_dnsmos_workspace_bytes(4096, 160000) == dlib.fsem_dnsmos_workspace_bytes(70000, 1 << 20)
-    assert golden["min"] < golden["dnsmos"][4] <= _native.DNSMOS_MAX_PASS * golden["min"]
-    assert dlib.fsem_dnsmos_workspace_bytes(4, 0) == 0 and dlib.fsem_dnsmos_workspace_bytes(1, (1 << 29) + 1) == 0
-
-
 def test_weights_file():
     from fast_speech_enhancement_metrics_amd.DNSMOS import WEIGHT_SHAPES, load_weights
     arrays = {}
@@ -79,20 +55,15 @@ def test_segment_counts(dlib):
 def test_abi_validation_without_launch(dlib):
     from fast_speech_enhancement_metrics_amd import _native
     null, p = None, ctypes.c_void_p(256)
-    big = 1 << 40
+    big, over = 1 << 40, (1 << 29) + 4
+    small = dlib.fsem_dnsmos_min_workspace_bytes()
+    ok = dict(deg=p, batch=4, length=160000, ld=160000, lengths=null, blob=p, out=p, ws=p, ws_bytes=big)
+    table = contract.nulled(_native.FSEM_EINVAL, "deg blob out") + contract.each(
+        _native.FSEM_EINVAL, dict(batch=0), dict(length=0, ld=0), dict(ld=159999),
+        dict(batch=1, length=over, ld=over, ws_bytes=1 << 62)) + contract.each(
+        _native.FSEM_EWORKSPACE, dict(ws_bytes=small - 1), dict(ws_bytes=16), dict(ws=null))
     for f in (dlib.fsem_dnsmos_f32, dlib.fsem_dnsmos_features_f32, dlib.fsem_dnsmos_raw_f32):
-        assert f(null, 4, 160000, 160000, null, p, p, p, big, null) == _native.FSEM_EINVAL
-        assert f(p, 4, 160000, 160000, null, null, p, p, big, null) == _native.FSEM_EINVAL
-        assert f(p, 4, 160000, 160000, null, p, null, p, big, null) == _native.FSEM_EINVAL
-        assert f(p, 0, 160000, 160000, null, p, p, p, big, null) == _native.FSEM_EINVAL
-        assert f(p, 4, 0, 0, null, p, p, p, big, null) == _native.FSEM_EINVAL
-        assert f(p, 4, 160000, 159999, null, p, p, p, big, null) == _native.FSEM_EINVAL
-        over = (1 << 29) + 4
-        assert f(p, 1, over, over, null, p, p, p, 1 << 62, null) == _native.FSEM_EINVAL
-        small = dlib.fsem_dnsmos_min_workspace_bytes()
-        assert f(p, 4, 160000, 160000, null, p, p, p, small - 1, null) == _native.FSEM_EWORKSPACE
-        assert f(p, 4, 160000, 160000, null, p, p, p, 16, null) == _native.FSEM_EWORKSPACE
-        assert f(p, 4, 160000, 160000, null, p, p, null, big, null) == _native.FSEM_EWORKSPACE
+        contract.refusals(contract.by_name(f, "deg batch length ld lengths blob out ws ws_bytes", null), ok, table)
     pack = dlib.fsem_dnsmos_pack_weights_f32
     ptrs = (ctypes.c_void_p * 22)(*([256] * 22))
     assert pack(None, p, big, null) == _native.FSEM_EINVAL and pack(ptrs, None, big, null) == _native.FSEM_EINVAL
@@ -143,17 +114,6 @@ def test_interface(metric):
     assert [[r[k] for k in DNSMOS.KEYS] for r in ragged] == [[float(v) for v in row] for row in by_len]
 
 
-def test_copy_and_pickle():
-    import copy
-    import pickle
-    x = dc.fixture("dnsmos_short").rows[:1]
-    m = DNSMOS(16000, use_gpu=False)
-    want = m(None, x)
-    for m2 in (copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
-        assert isinstance(m2, DNSMOS) and m2.sample_rate == 16000 and m2.weights_file == m.weights_file
-        assert m2(None, x) == want
-
-
 def test_alias_path_and_exports():
     import fast_se_metrics
     import fast_speech_enhancement_metrics_amd as pkg
@@ -200,13 +160,3 @@ def test_nonfinite_and_empty_rows_are_nan_alone(metric):
     assert all(np.isnan(v) for v in res[1].values()) and list(res[1]) == list(DNSMOS.KEYS)
     assert [res[b][k] for b in (0, 2) for k in DNSMOS.KEYS] == [float(v) for v in base[[0, 2]].reshape(-1)]
     assert torch.isnan(metric.scores(x[:, :0])).all()
-
-
-if __name__ == "__main__":
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    with open(WS_GOLDEN, "w") as f:
-        json.dump({"pairs": [list(p) for p in PAIRS], **record_workspace(_native.load_dnsmos())}, f,
-                  separators=(",", ":"))
-        f.write("\n")
-    print("wrote", WS_GOLDEN)

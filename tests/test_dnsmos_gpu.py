@@ -11,6 +11,7 @@ import torch
 from fast_speech_enhancement_metrics_amd import DNSMOS, _native
 
 from . import dnsmos_cases as dc
+from .contract import assert_bitwise, on_side_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -18,14 +19,6 @@ pytestmark = pytest.mark.gpu
 # stored basis: the basis is a sample of the f16 rounding noise of the network, and no row of the
 # fixtures showed more.
 SCORE_BAR = 2 * max(dc.fixture(n).basis for n in dc.FIXTURES)
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def assert_bitwise(got, want, what=""):
-    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
 
 
 @pytest.fixture(scope="module")
@@ -130,11 +123,7 @@ def test_rows_score_as_the_row_alone(metric, ragged):
     view.copy_(g)
     assert view.data_ptr() % 16 == 4 and view.stride(0) == ld
     assert_bitwise(metric.scores(view, lengths=list(RAGGED)), got, "odd ld, offset base")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        s = metric.scores(g, lengths=list(RAGGED))
-    side.synchronize()
+    s = on_side_stream(lambda: metric.scores(g, lengths=list(RAGGED)))
     assert_bitwise(s, got, "side stream")
 
 

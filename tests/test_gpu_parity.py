@@ -7,16 +7,16 @@ import pytest
 import torch
 
 from tests.conftest import PESQ_CASES, STOI_CASES, load_golden
+from tests import contract
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
     from fast_speech_enhancement_metrics_amd import _native
     _native.load()
-    return torch.device("cuda:0")
+    return contract.device()
 
 
 def test_native_library_is_loaded(dev):

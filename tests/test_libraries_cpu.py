@@ -10,6 +10,8 @@ import pytest
 
 from fast_speech_enhancement_metrics_amd import _build, _native
 
+from . import contract
+
 # the entry set of each library after the core, pinned name by name
 ENTRIES = {
     "composite": {"fsem_composite_chunk", "fsem_composite_workspace_bytes", "fsem_composite_f32"},
@@ -24,8 +26,7 @@ ENTRIES = {
 
 @pytest.fixture(scope="module")
 def lib():
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 def declared(entry) -> set:

@@ -1,12 +1,6 @@
 """LSD metric without a GPU: the CPU mode against the float64 statement of the definition
 (tests/lsd_cases.py) and the reference's own scores (tests/golden/lsd_*.npz), the edge semantics,
 the drop-in call, the C-ABI's host-side queries and validation (no launch), copying and pickling."""
-import copy
-import ctypes
-import json
-import os
-import pickle
-
 import numpy as np
 import pytest
 import torch
@@ -14,16 +8,13 @@ import torch
 from fast_speech_enhancement_metrics_amd import LSD, _cpu
 
 from . import lsd_cases as lc
-from .test_workspace_cpu import PAIRS
-
-WS_GOLDEN = os.path.join(lc.GOLDEN, "lsd_workspace_bytes.json")
+from . import contract
+from . import pair_metrics as pm
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 @pytest.fixture(scope="module")
@@ -108,15 +99,7 @@ def test_empty_row_in_a_ragged_list():
 
 
 def test_nonfinite_row_is_nan_alone():
-    c, n = lc.speech_rows(4, 8000)
-    n2, c2 = n.clone(), c.clone()
-    n2[1, 4000] = float("nan")
-    c2[3, 17] = float("inf")
-    m = LSD(16000)
-    base, got = m.scores(c, n), m.scores(c2, n2)
-    assert torch.isnan(got[[1, 3]]).all()
-    assert torch.equal(got[[0, 2]], base[[0, 2]])
-    lc.assert_close(got, lc.expected(c2, n2), "cpu non-finite")
+    pm.nonfinite_row_is_nan_alone("LSD")
 
 
 def test_drop_in_call_key_order_and_shape_check():
@@ -138,15 +121,6 @@ def test_drop_in_call_key_order_and_shape_check():
     assert DropIn is LSD
 
 
-def test_copy_and_pickle():
-    c, n = lc.speech_rows(2, 12000, sr=8000)
-    m = LSD(8000, use_gpu=False)
-    want = m(c, n)
-    for m2 in (copy.copy(m), copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
-        assert isinstance(m2, LSD) and m2.sample_rate == 8000 and m2.nfft == 512
-        assert m2(c, n) == want
-
-
 # ------------------------------------------------------------------ the C-ABI, host side
 def test_abi_geometry(llib):
     C = llib.fsem_lsd_chunk()
@@ -155,47 +129,5 @@ def test_abi_geometry(llib):
         assert llib.fsem_lsd_frames(n) == 1 + n // 256
 
 
-def record_workspace(llib) -> list:
-    return [llib.fsem_lsd_workspace_bytes(b, l) for b, l in PAIRS]
-
-
-def test_workspace_sizes_equal_the_recorded_ones(llib):
-    """fsem_lsd_workspace_bytes is pinned to tests/golden/lsd_workspace_bytes.json on
-    test_workspace_cpu's PAIRS (python -m tests.test_lsd_cpu re-records)."""
-    with open(WS_GOLDEN) as f:
-        golden = json.load(f)
-    assert golden["pairs"] == [list(p) for p in PAIRS]
-    assert record_workspace(llib) == golden["lsd"]
-    assert all(golden["lsd"][:-1]) and golden["lsd"][-1] == 0  # (last pair: batch 0)
-    assert llib.fsem_lsd_workspace_bytes(4, 0) == 0 and llib.fsem_lsd_workspace_bytes(1, (1 << 29) + 1) == 0
-
-
 def test_abi_validation_without_launch(llib):
-    from fast_speech_enhancement_metrics_amd import _native
-    null, p = None, ctypes.c_void_p(16)
-    f = llib.fsem_lsd_f32
-    big = 1 << 40
-    assert f(null, null, 4, 160000, 160000, null, null, null, 0, null) == _native.FSEM_EINVAL
-    assert f(null, p, 4, 160000, 160000, null, p, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, null, 4, 160000, 160000, null, p, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, p, 4, 160000, 160000, null, null, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, p, 0, 160000, 160000, null, p, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, p, 4, 0, 0, null, p, p, big, null) == _native.FSEM_EINVAL
-    assert f(p, p, 4, 160000, 159999, null, p, p, big, null) == _native.FSEM_EINVAL
-    over = (1 << 29) + 4
-    assert f(p, p, 1, over, over, null, p, p, 1 << 62, null) == _native.FSEM_EINVAL
-    size = llib.fsem_lsd_workspace_bytes(4, 160000)
-    assert size > 0
-    assert f(p, p, 4, 160000, 160000, null, p, p, 16, null) == _native.FSEM_EWORKSPACE
-    assert f(p, p, 4, 160000, 160000, null, p, p, size - 1, null) == _native.FSEM_EWORKSPACE
-    assert f(p, p, 4, 160000, 160000, null, p, null, big, null) == _native.FSEM_EWORKSPACE
-
-
-if __name__ == "__main__":
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    with open(WS_GOLDEN, "w") as f:
-        json.dump({"pairs": [list(p) for p in PAIRS], "lsd": record_workspace(_native.load_lsd())}, f,
-                  separators=(",", ":"))
-        f.write("\n")
-    print("wrote", WS_GOLDEN)
+    pm.one_output_validation(llib, "lsd")

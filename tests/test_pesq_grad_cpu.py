@@ -9,8 +9,6 @@ differences run along random directions scaled to the row's norm at steps 1e-5 a
 and above the quotient crosses the jump at a = 3, where the function is discontinuous, and stops converging."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +16,7 @@ import torch
 
 from fast_speech_enhancement_metrics_amd import PESQ, _build, _cpu, _native
 
+from . import contract
 from . import pesq_grad_cases as gc
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -27,25 +26,12 @@ NAMES = ["main", "short", "long", "odd", "zero", "bad"]
 
 @pytest.fixture(scope="module")
 def lib():
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 def test_entries_are_declared_exported_and_bound(lib):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "fsem.h")).read(), flags=re.S)
-    out = subprocess.run(["nm", "-D", "--defined-only", _build.LIB], capture_output=True, text=True, check=True).stdout
-    exported = {n for n in re.findall(r" T (fsem_pesq_[a-z0-9_]+)", out)}
-    declared = set(re.findall(r"\b(fsem_pesq_[a-z0-9_]+)\s*\(", header))
-    bound = {n for n in _native.SIGNATURES if n.startswith("fsem_pesq_")}
-    assert exported == declared == bound and set(ENTRIES) <= bound
-    for name in ENTRIES:
-        fn = getattr(lib, name)
-        assert fn.restype is _native.SIGNATURES[name][0] and fn.argtypes == _native.SIGNATURES[name][1]
-        assert ctypes.c_size_t not in _native.SIGNATURES[name][1] and not name.endswith("_workspace_bytes")
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, header)
-        assert "size_t" not in m.group(1) and m.group(1).count(",") + 1 == len(_native.SIGNATURES[name][1])
+    contract.entries_are_declared_exported_and_bound(lib, "fsem_pesq_", ENTRIES, None)  # (the others: test_abi_cpu)
     assert "pesq_grad.hip" in _build.SOURCES and "pesq_grad.hip" not in _build.SOURCE_FLAGS
-    assert lib.fsem_version() == 11
 
 
 def test_state_floats(lib):
@@ -64,33 +50,19 @@ def test_abi_refuses_before_launch(lib):
     # (no GPU here: a launch would come back as FSEM_ELAUNCH; dummy non-null pointers are never read)
     p, null = ctypes.c_void_p(256), None
     big = (1 << 29) + 4
+    EINVAL, OK = _native.FSEM_EINVAL, _native.FSEM_OK
     shapes = (dict(batch=-1), dict(length=0), dict(length=-4), dict(ld=15999), dict(length=big, ld=big))
+    fwd = contract.by_name(lib.fsem_pesq_state_f32, "ref deg batch length ld lengths mos dist state", null)
     ok = dict(ref=p, deg=p, batch=3, length=16000, ld=16000, lengths=null, mos=p, dist=p, state=p)
-
-    def fwd(**kw):
-        a = {**ok, **kw}
-        return lib.fsem_pesq_state_f32(a["ref"], a["deg"], a["batch"], a["length"], a["ld"], a["lengths"], a["mos"],
-                                       a["dist"], a["state"], null)
-
-    for name in ("ref", "deg", "mos", "state"):
-        assert fwd(**{name: null}) == _native.FSEM_EINVAL, name
-    for kw in shapes:
-        assert fwd(**kw) == _native.FSEM_EINVAL, kw
-    assert fwd(length=4000, ld=4000) == _native.FSEM_ESHORT   # under 20 frames without lengths, as fsem_pesq_wb_f32
-    for kw in (dict(), dict(lengths=p), dict(dist=null)):
-        assert fwd(batch=0, **kw) == _native.FSEM_OK, kw  # nothing launched
+    contract.refusals(fwd, ok, contract.nulled(EINVAL, "ref deg mos state") + contract.each(EINVAL, *shapes) + [
+        (dict(length=4000, ld=4000), _native.FSEM_ESHORT)])  # under 20 frames without lengths, as fsem_pesq_wb_f32
+    # nothing launched
+    contract.refusals(fwd, dict(ok, batch=0), contract.each(OK, dict(), dict(lengths=p), dict(dist=null)))
+    bwd = contract.by_name(lib.fsem_pesq_grad_f32, "deg batch length ld lengths state gm gs ga grad grad_ld", null)
     okg = dict(deg=p, batch=3, length=16000, ld=16000, lengths=null, state=p, gm=p, gs=p, ga=p, grad=p, grad_ld=16000)
-
-    def bwd(**kw):
-        a = {**okg, **kw}
-        return lib.fsem_pesq_grad_f32(a["deg"], a["batch"], a["length"], a["ld"], a["lengths"], a["state"], a["gm"],
-                                      a["gs"], a["ga"], a["grad"], a["grad_ld"], null)
-
-    for name in ("deg", "state", "gm", "grad"):
-        assert bwd(**{name: null}) == _native.FSEM_EINVAL, name
-    for kw in shapes + (dict(grad_ld=15999),):
-        assert bwd(**kw) == _native.FSEM_EINVAL, kw
-    assert bwd(batch=0) == _native.FSEM_OK and bwd(batch=0, lengths=p, gs=null, ga=null) == _native.FSEM_OK
+    contract.refusals(bwd, okg, contract.nulled(EINVAL, "deg state gm grad")
+                      + contract.each(EINVAL, *shapes, dict(grad_ld=15999))
+                      + contract.each(OK, dict(batch=0), dict(batch=0, lengths=p, gs=null, ga=null)))
 
 
 def test_the_cases_score_what_they_should():

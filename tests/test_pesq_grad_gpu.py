@@ -16,14 +16,11 @@ import torch
 from fast_speech_enhancement_metrics_amd import PESQ, _native
 
 from . import pesq_grad_cases as gc
+from .contract import bits
 
 pytestmark = pytest.mark.gpu
 NAMES = ["main", "short", "long", "odd", "zero", "bad"]
 ATOL_SCORE = 5e-3   # MOS against float64: the bar the smoke run holds the forward to (the subject here is the bitwise check)
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
 
 
 def engine(c, d, lengths=None, g=None):
@@ -59,8 +56,8 @@ def test_forward_is_scores_bitwise(name):
     m = PESQ(16000, use_gpu=True)
     s0 = m.scores(c.cuda(), d.cuda().requires_grad_(True))
     assert s0.grad_fn is None and not s0.requires_grad
-    np.testing.assert_array_equal(_bits(mos), _bits(s0))
-    np.testing.assert_array_equal(_bits(m.differentiable_scores(c.cuda(), d.cuda())), _bits(s0))
+    np.testing.assert_array_equal(bits(mos), bits(s0))
+    np.testing.assert_array_equal(bits(m.differentiable_scores(c.cuda(), d.cuda())), bits(s0))
     want = gc.expected(name)["scores"]
     got = torch.stack([mos, sym, asym], 1).cpu().numpy()
     live = np.isfinite(want[:, 0])
@@ -85,7 +82,7 @@ def test_gradient_against_the_reference(name, u):
         c, d = gc.rows(name)
         for b in (0, 2):
             alone = engine(c[b:b + 1], d[b:b + 1], g=tuple(v[b:b + 1] for v in g))[3]
-            np.testing.assert_array_equal(_bits(alone[0]), _bits(torch.from_numpy(grad[b])))
+            np.testing.assert_array_equal(bits(alone[0]), bits(torch.from_numpy(grad[b])))
 
 
 def test_an_infinite_sample_zeroes_its_row_only():
@@ -95,7 +92,7 @@ def test_an_infinite_sample_zeroes_its_row_only():
     bad[1, 5000] = float("inf")
     grad = engine(c, bad, g=g)[3]
     assert (grad[1] == 0).all()
-    np.testing.assert_array_equal(_bits(grad[[0, 2, 3]]), _bits(base[[0, 2, 3]]))
+    np.testing.assert_array_equal(bits(grad[[0, 2, 3]]), bits(base[[0, 2, 3]]))
 
 
 def test_ragged_rows():
@@ -120,25 +117,25 @@ def test_ragged_rows():
         nb = lens[b]
         pad = (-nb) % 4
         m1, _, _, g1 = engine(c[b:b + 1, :nb + pad], d[b:b + 1, :nb + pad], lengths=[nb], g=tuple(v[:1] for v in g))
-        np.testing.assert_array_equal(_bits(m1), _bits(mos[b:b + 1]))
-        np.testing.assert_array_equal(_bits(g1[0, :nb]), _bits(grad[b, :nb]))
+        np.testing.assert_array_equal(bits(m1), bits(mos[b:b + 1]))
+        np.testing.assert_array_equal(bits(g1[0, :nb]), bits(grad[b, :nb]))
     c2, d2 = c.clone(), d.clone()
     c2[1, lens[1] + 3:], d2[1, lens[1] + 3:] = float("nan"), float("inf")   # (past ceil4 of the row's length)
-    np.testing.assert_array_equal(_bits(engine(c2, d2, lengths=lens, g=g)[3]), _bits(grad))
+    np.testing.assert_array_equal(bits(engine(c2, d2, lengths=lens, g=g)[3]), bits(grad))
 
 
 def test_reproducible_and_batch_independent():
     c, d = gc.rows("main")
     _, _, _, base, g = engine_set("main", gc.UPSTREAMS[0])
-    np.testing.assert_array_equal(_bits(engine(c, d, g=g)[3]), _bits(base))
+    np.testing.assert_array_equal(bits(engine(c, d, g=g)[3]), bits(base))
     for b in range(4):
         alone = engine(c[b:b + 1], d[b:b + 1], g=tuple(v[b:b + 1] for v in g))[3]
-        np.testing.assert_array_equal(_bits(alone[0]), _bits(base[b]))
+        np.testing.assert_array_equal(bits(alone[0]), bits(base[b]))
     # the long row alone and as row 1 of a batch of two
     c, d = gc.rows("long")
     _, _, _, base, g = engine_set("long", gc.UPSTREAMS[0])
     two = engine(torch.cat([c, c]), torch.cat([d * 0.5, d]), g=tuple(v.repeat(2) for v in g))[3]
-    np.testing.assert_array_equal(_bits(two[1]), _bits(base[0]))
+    np.testing.assert_array_equal(bits(two[1]), bits(base[0]))
 
 
 def test_scale_invariance():
@@ -146,8 +143,8 @@ def test_scale_invariance():
     mos, _, _, base, g = engine_set("main", gc.UPSTREAMS[0])
     for k in (3, -3):
         m2, _, _, grad = engine(c, d * 2.0 ** k, g=g)
-        np.testing.assert_array_equal(_bits(m2), _bits(mos))
-        np.testing.assert_array_equal(_bits(grad * 2.0 ** k), _bits(base))
+        np.testing.assert_array_equal(bits(m2), bits(mos))
+        np.testing.assert_array_equal(bits(grad * 2.0 ** k), bits(base))
     # <g, x> = 0: the score does not depend on the scale of x
     for name in ("main", "short", "long"):
         c, d = gc.rows(name)
@@ -167,7 +164,7 @@ def test_row_layouts():
     est = wide.requires_grad_(True)
     mos = m.differentiable_scores(cwide[:, 12:16012], est[:, 12:16012])   # slices: the engine reads them in place
     mos.backward(g[0].cuda())
-    np.testing.assert_array_equal(_bits(est.grad[:, 12:16012]), _bits(base))
+    np.testing.assert_array_equal(bits(est.grad[:, 12:16012]), bits(base))
     assert (est.grad[:, :12] == 0).all() and (est.grad[:, 16012:] == 0).all()
     # a non-contiguous estimate (every other column) comes back in the caller's shape
     inter = torch.zeros(4, 32000).cuda()
@@ -175,14 +172,14 @@ def test_row_layouts():
     est = inter.requires_grad_(True)
     m.differentiable_scores(c.cuda(), est[:, ::2]).backward(g[0].cuda())
     assert est.grad.shape == (4, 32000) and (est.grad[:, 1::2] == 0).all()
-    np.testing.assert_array_equal(_bits(est.grad[:, ::2]), _bits(base))
+    np.testing.assert_array_equal(bits(est.grad[:, ::2]), bits(base))
     # an odd length against its zero-padded copy with lengths
     c, d = gc.rows("odd")
     _, _, _, odd, g = engine_set("odd", gc.UPSTREAMS[0])
     assert odd.shape == (4, gc.ODD_LENGTH)
     pad = torch.nn.functional.pad
     padded = engine(pad(c, (0, 3)), pad(d, (0, 3)), lengths=[gc.ODD_LENGTH] * 4, g=g)[3]
-    np.testing.assert_array_equal(_bits(padded[:, :gc.ODD_LENGTH]), _bits(odd))
+    np.testing.assert_array_equal(bits(padded[:, :gc.ODD_LENGTH]), bits(odd))
     # half precision estimates: cast to float32, the gradient back in their dtype
     half = d.cuda().to(torch.bfloat16).requires_grad_(True)
     m.loss(c.cuda(), half).backward()
@@ -210,7 +207,7 @@ def test_loss_and_a_retained_graph():
         assert err.max() <= gc.bar() and (first[3] == 0).all()
         est.grad = None
         loss.backward()   # a second backward through the retained graph: the same bits
-        np.testing.assert_array_equal(_bits(est.grad), _bits(first))
+        np.testing.assert_array_equal(bits(est.grad), bits(first))
     short = d[:, :3000].cuda().requires_grad_(True)
     loss = m.loss(c[:, :3000].cuda(), short, lengths=[3000] * 4)
     assert float(loss.detach()) == 0.0
@@ -240,17 +237,17 @@ def test_c_entries_directly():
     st = _native.stream_handle(cd.device)
     assert lib.fsem_pesq_state_f32(p(cd), p(nd), B, L, ld, None, p(mos), p(dist), p(state), st) == _native.FSEM_OK
     m0, s0, a0, base, g = engine_set("short", gc.UPSTREAMS[0])
-    np.testing.assert_array_equal(_bits(mos), _bits(m0))
-    np.testing.assert_array_equal(_bits(dist), _bits(torch.stack([s0, a0])))
+    np.testing.assert_array_equal(bits(mos), bits(m0))
+    np.testing.assert_array_equal(bits(dist), bits(torch.stack([s0, a0])))
     mos2 = torch.empty(B, device="cuda")   # without the distances: the scoring instance, the same bits
     assert lib.fsem_pesq_state_f32(p(cd), p(nd), B, L, ld, None, p(mos2), None, p(state), st) == _native.FSEM_OK
-    np.testing.assert_array_equal(_bits(mos2), _bits(m0))
+    np.testing.assert_array_equal(bits(mos2), bits(m0))
     grad = torch.full((B, grad_ld), 7.0, device="cuda")
     gm = g[0].cuda()
     for _ in range(2):   # (the state may be read again)
         assert lib.fsem_pesq_grad_f32(p(nd), B, L, ld, None, p(state), p(gm), None, None, p(grad), grad_ld, st) == \
             _native.FSEM_OK
-        np.testing.assert_array_equal(_bits(grad[:, :L]), _bits(base))
+        np.testing.assert_array_equal(bits(grad[:, :L]), bits(base))
         assert (grad[:, L:] == 7.0).all()   # the padding columns are not written
     # refusals come back before any launch
     assert lib.fsem_pesq_grad_f32(p(nd), B, L, ld, None, p(state), p(gm), None, None, p(grad), L - 1, st) == \
@@ -260,4 +257,4 @@ def test_c_entries_directly():
         assert lib.fsem_pesq_grad_f32(args[0], B, L, ld, None, args[1], args[2], None, None, args[3], grad_ld, st) == \
             _native.FSEM_EINVAL
     assert (grad[:, L:] == 7.0).all()
-    np.testing.assert_array_equal(_bits(grad[:, :L]), _bits(base))
+    np.testing.assert_array_equal(bits(grad[:, :L]), bits(base))

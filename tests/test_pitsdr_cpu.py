@@ -9,8 +9,6 @@ they are checked to be exactly the float32 rounding of those float64 values."""
 import ctypes
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +16,7 @@ import torch
 
 from fast_speech_enhancement_metrics_amd import PITSDR, SDR, _build, _cpu, _native
 
+from . import contract
 from . import pitsdr_cases as pc
 from . import sdr_cases as sc
 
@@ -28,8 +27,7 @@ ENTRIES = ("fsem_pitsdr_max_sources", "fsem_pitsdr_chunk", "fsem_pitsdr_sums_dou
 
 @pytest.fixture(scope="module")
 def lib():
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 @pytest.fixture(scope="module")
@@ -51,17 +49,8 @@ def cpu64(metric, s, h, lengths=None, criterion="SI-SDR"):
 
 
 def test_entries_are_declared_exported_and_bound(lib):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "fsem.h")).read(), flags=re.S)
-    out = subprocess.run(["nm", "-D", "--defined-only", _build.LIB], capture_output=True, text=True, check=True).stdout
-    exported = {n for n in re.findall(r" T (fsem_[a-z0-9_]+)", out) if n.startswith("fsem_pitsdr_")}
-    declared = set(re.findall(r"\b(fsem_pitsdr_[a-z0-9_]+)\s*\(", header))
-    bound = {n for n in _native.SIGNATURES if n.startswith("fsem_pitsdr_")}
-    assert exported == declared == bound == set(ENTRIES)
-    for name in ENTRIES:
-        fn = getattr(lib, name)
-        assert fn.restype is _native.SIGNATURES[name][0] and fn.argtypes == _native.SIGNATURES[name][1]
-        assert ctypes.c_size_t not in _native.SIGNATURES[name][1] and not name.endswith("_workspace_bytes")
-    assert "pitsdr.hip" in _build.SOURCES and lib.fsem_version() == 11
+    contract.entries_are_declared_exported_and_bound(lib, "fsem_pitsdr_", ENTRIES)
+    assert "pitsdr.hip" in _build.SOURCES
 
 
 def test_queries(lib):
@@ -85,37 +74,22 @@ def test_abi_refuses_before_launch(lib):
     # (no GPU here: a launch would come back as FSEM_ELAUNCH; dummy non-null pointers are never read)
     p, null = ctypes.c_void_p(16), None
     big = (1 << 29) + 1
+    EINVAL, ERATE, OK = _native.FSEM_EINVAL, _native.FSEM_ERATE, _native.FSEM_OK
     shapes = (dict(batch=-1), dict(S=0), dict(S=5), dict(E=0), dict(E=5), dict(S=2, E=3), dict(length=0),
               dict(ld=7999), dict(length=big, ld=big))
+    fwd = contract.by_name(lib.fsem_pitsdr_f32, "src est batch S E length ld lengths sr zm crit sums si snr perm", null)
     ok = dict(src=p, est=p, batch=3, S=2, E=2, length=8000, ld=8000, lengths=null, sr=16000, zm=0, crit=1, sums=p,
               si=p, snr=p, perm=p)
-
-    def fwd(**kw):
-        a = {**ok, **kw}
-        return lib.fsem_pitsdr_f32(a["src"], a["est"], a["batch"], a["S"], a["E"], a["length"], a["ld"], a["lengths"],
-                                   a["sr"], a["zm"], a["crit"], a["sums"], a["si"], a["snr"], a["perm"], null)
-
-    for name in ("src", "est", "sums", "si", "snr", "perm"):
-        assert fwd(**{name: null}) == _native.FSEM_EINVAL, name
-    for kw in shapes + (dict(crit=-1), dict(crit=3)):
-        assert fwd(**kw) == _native.FSEM_EINVAL, kw
-    for sr in (3999, 192001, 0):
-        assert fwd(sr=sr) == _native.FSEM_ERATE, sr
-    assert fwd(batch=0) == _native.FSEM_OK and fwd(batch=0, lengths=p) == _native.FSEM_OK  # nothing launched
+    contract.refusals(fwd, ok, contract.nulled(EINVAL, "src est sums si snr perm")
+                      + contract.each(EINVAL, *shapes, dict(crit=-1), dict(crit=3))
+                      + contract.each(ERATE, dict(sr=3999), dict(sr=192001), dict(sr=0))
+                      + contract.each(OK, dict(batch=0), dict(batch=0, lengths=p)))  # nothing launched
+    bwd = contract.by_name(lib.fsem_pitsdr_grad_f32,
+                           "src est batch S E length ld lengths zm sums g_si g_snr grad grad_ld", null)
     okg = dict(src=p, est=p, batch=3, S=2, E=2, length=8000, ld=8000, lengths=null, zm=0, sums=p, g_si=p, g_snr=p,
                grad=p, grad_ld=8000)
-
-    def bwd(**kw):
-        a = {**okg, **kw}
-        return lib.fsem_pitsdr_grad_f32(a["src"], a["est"], a["batch"], a["S"], a["E"], a["length"], a["ld"],
-                                        a["lengths"], a["zm"], a["sums"], a["g_si"], a["g_snr"], a["grad"],
-                                        a["grad_ld"], null)
-
-    for name in ("src", "est", "sums", "g_si", "g_snr", "grad"):
-        assert bwd(**{name: null}) == _native.FSEM_EINVAL, name
-    for kw in shapes + (dict(grad_ld=7999),):
-        assert bwd(**kw) == _native.FSEM_EINVAL, kw
-    assert bwd(batch=0) == _native.FSEM_OK
+    contract.refusals(bwd, okg, contract.nulled(EINVAL, "src est sums g_si g_snr grad")
+                      + contract.each(EINVAL, *shapes, dict(grad_ld=7999)) + contract.each(OK, dict(batch=0)))
 
 
 @pytest.mark.parametrize("shape", pc.SHAPES, ids=lambda s: "S%d-E%d-n%d" % s)

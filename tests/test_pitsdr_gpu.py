@@ -16,18 +16,9 @@ from fast_speech_enhancement_metrics_amd import PITSDR, _native
 
 from . import pitsdr_cases as pc
 from . import sdr_cases as sc
+from .contract import assert_bitwise, on_side_stream
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.uint32 if t.dtype == torch.float32 else np.int32)
-
-
-def assert_bitwise(got, want, what=""):
-    assert len(got) == len(want)
-    for k, (g, w) in enumerate(zip(got, want)):
-        np.testing.assert_array_equal(_bits(g), _bits(w), err_msg=f"{what} [{k}]")
 
 
 def run(m, s, h, lengths=None, g=None):
@@ -110,11 +101,7 @@ def test_layouts_are_bitwise_equal(ragged):
         got = run(m, sv, hv, lens, g)
         assert_bitwise(got[0], base[0], what)
         assert_bitwise([got[1]], [base[1]], what + ", gradient")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        got = run(m, sg, hg, lens, g)
-    side.synchronize()
+    got = on_side_stream(lambda: run(m, sg, hg, lens, g))
     assert_bitwise(got[0], base[0], "side stream")
     assert_bitwise([got[1]], [base[1]], "side stream, gradient")
 

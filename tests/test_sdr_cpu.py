@@ -1,10 +1,8 @@
 """SDR metric (SI-SDR, SNR, segmental SNR) without a GPU: the CPU mode against the float64
 statement of the definitions (tests/sdr_cases.py), the edge semantics, the drop-in call, the
 C-ABI's host-side queries and validation (no launch), copying and pickling."""
-import copy
 import ctypes
 import math
-import pickle
 
 import numpy as np
 import pytest
@@ -13,13 +11,13 @@ import torch
 from fast_speech_enhancement_metrics_amd import SDR
 
 from . import sdr_cases as sc
+from . import contract
+from . import pair_metrics as pm
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 @pytest.mark.parametrize("sr", [8000, 16000, 22050, 48000])
@@ -100,15 +98,7 @@ def test_drop_in_call_and_shape_check():
 
 
 def test_nonfinite_row_is_nan_alone():
-    c, n = sc.speech_rows(4, 8000, 16000)
-    n2, c2 = n.clone(), c.clone()
-    n2[1, 4000] = float("nan")
-    c2[3, 17] = float("inf")
-    m = SDR(16000)
-    base, got = m.scores(c, n), m.scores(c2, n2)
-    for b, g in zip(base, got):
-        assert torch.isnan(g[[1, 3]]).all()
-        assert torch.equal(g[[0, 2]], b[[0, 2]])
+    pm.nonfinite_row_is_nan_alone("SDR")
 
 
 def test_abi_geometry(lib):
@@ -130,23 +120,12 @@ def test_abi_geometry(lib):
 def test_abi_validation_without_launch(lib):
     from fast_speech_enhancement_metrics_amd import _native
     null, p = None, ctypes.c_void_p(16)
-    assert lib.fsem_sdr_f32(null, null, 4, 160000, 160000, null, 16000, 0, null, null, null, null, 0, null) == -1
-    assert lib.fsem_sdr_f32(p, p, 4, 160000, 160000, null, 16000, 0, p, p, null, p, 1 << 40, null) == -1
-    assert lib.fsem_sdr_f32(p, p, 0, 160000, 160000, null, 16000, 0, p, p, p, p, 1 << 40, null) == -1
-    assert lib.fsem_sdr_f32(p, p, 4, 0, 0, null, 16000, 0, p, p, p, p, 1 << 40, null) == -1
-    assert lib.fsem_sdr_f32(p, p, 4, 160000, 159999, null, 16000, 0, p, p, p, p, 1 << 40, null) == -1
-    for sr in (3999, 200000):
-        assert lib.fsem_sdr_f32(p, p, 4, 160000, 160000, null, sr, 0, p, p, p, p, 1 << 40, null) == _native.FSEM_ERATE
-    assert lib.fsem_sdr_f32(p, p, 4, 160000, 160000, null, 16000, 0, p, p, p, p, 16, null) == -2
-    assert lib.fsem_sdr_f32(p, p, 4, 160000, 160000, null, 16000, 0, p, p, p, null, 1 << 40, null) == -2
     big = (1 << 29) + 4
-    assert lib.fsem_sdr_f32(p, p, 1, big, big, null, 16000, 0, p, p, p, p, 1 << 62, null) == -1
-
-
-def test_copy_and_pickle():
-    c, n = sc.speech_rows(2, 16000, 16000)
-    m = SDR(16000, use_gpu=False, zero_mean=True)
-    want = m(c, n)
-    for m2 in (copy.copy(m), copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
-        assert isinstance(m2, SDR) and m2.zero_mean and m2.sample_rate == 16000
-        assert m2(c, n) == want
+    call = contract.by_name(lib.fsem_sdr_f32, "ref deg batch length ld lengths sr zm si snr seg ws ws_bytes", null)
+    ok = dict(ref=p, deg=p, batch=4, length=160000, ld=160000, lengths=null, sr=16000, zm=0, si=p, snr=p, seg=p, ws=p,
+              ws_bytes=1 << 40)
+    contract.refusals(call, ok, contract.each(
+        _native.FSEM_EINVAL, dict(ref=null, deg=null, si=null, snr=null, seg=null, ws=null, ws_bytes=0), dict(seg=null),
+        dict(batch=0), dict(length=0, ld=0), dict(ld=159999), dict(batch=1, length=big, ld=big, ws_bytes=1 << 62))
+        + contract.each(_native.FSEM_ERATE, dict(sr=3999), dict(sr=200000))
+        + contract.each(_native.FSEM_EWORKSPACE, dict(ws_bytes=16), dict(ws=null)))

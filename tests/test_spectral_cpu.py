@@ -14,6 +14,7 @@ from fast_speech_enhancement_metrics_amd import SpectralMeasures, _build, _cpu, 
 
 from . import sdr_cases
 from . import spectral_cases as sp
+from . import contract
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 CSRC = os.path.join(REPO, "fast_speech_enhancement_metrics_amd", "csrc")
@@ -21,8 +22,7 @@ CSRC = os.path.join(REPO, "fast_speech_enhancement_metrics_amd", "csrc")
 
 @pytest.fixture(scope="module")
 def lib():
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 def test_order_and_frames(lib):
@@ -36,31 +36,21 @@ def test_order_and_frames(lib):
 def test_abi_refuses_before_launch(lib):
     # (no GPU here: a launch would come back as FSEM_ELAUNCH; dummy non-null pointers are never read)
     p, null = ctypes.c_void_p(16), None
-    B, L = 3, 8000
+    B, L, big = 3, 8000, (1 << 29) + 1
+    EINVAL, OK = _native.FSEM_EINVAL, _native.FSEM_OK
+    call = contract.by_name(lib.fsem_spectral_f32, "ref deg batch length ld lengths sr frames ldf fw cd is_", null)
+    ok = dict(ref=p, deg=p, batch=B, length=L, ld=L, lengths=null, frames=p, fw=p, cd=p, is_=p)
     for sr in (8000, 16000):
         F = lib.fsem_sdr_frames(L, sr)
-        ok = dict(ref=p, deg=p, batch=B, length=L, ld=L, lengths=null, sr=sr, frames=p, ldf=F, fw=p, cd=p, is_=p)
-
-        def call(**kw):
-            a = {**ok, **kw}
-            return lib.fsem_spectral_f32(a["ref"], a["deg"], a["batch"], a["length"], a["ld"], a["lengths"], a["sr"],
-                                         a["frames"], a["ldf"], a["fw"], a["cd"], a["is_"], null)
-
-        for name in ("ref", "deg", "frames", "fw", "cd", "is_"):
-            assert call(**{name: null}) == _native.FSEM_EINVAL, name
-        assert call(ldf=F - 1) == _native.FSEM_EINVAL
-        assert call(ldf=0) == _native.FSEM_EINVAL
-        assert call(length=0, ld=0, ldf=0) == _native.FSEM_EINVAL  # ldf >= max(F, 1)
-        assert call(batch=-1) == _native.FSEM_EINVAL
-        assert call(length=-1) == _native.FSEM_EINVAL
-        assert call(ld=L - 1) == _native.FSEM_EINVAL
-        big = (1 << 29) + 1
-        assert call(length=big, ld=big, ldf=1 << 29) == _native.FSEM_EINVAL
-        assert call(batch=0) == _native.FSEM_OK  # nothing to score, nothing launched
-        assert call(batch=0, length=0, ld=0, ldf=1) == _native.FSEM_OK
+        contract.refusals(call, dict(ok, sr=sr, ldf=F), contract.nulled(EINVAL, "ref deg frames fw cd is_")
+                          + contract.each(EINVAL, dict(ldf=F - 1), dict(ldf=0),
+                                          dict(length=0, ld=0, ldf=0),  # ldf >= max(F, 1)
+                                          dict(batch=-1), dict(length=-1), dict(ld=L - 1),
+                                          dict(length=big, ld=big, ldf=1 << 29))
+                          # nothing to score, nothing launched
+                          + contract.each(OK, dict(batch=0), dict(batch=0, length=0, ld=0, ldf=1)))
     for sr in (0, 4000, 11025, 22050, 44100, 48000):
-        rc = lib.fsem_spectral_f32(p, p, B, L, L, null, sr, p, L, p, p, p, null)
-        assert rc == _native.FSEM_ERATE, sr
+        contract.refusals(call, dict(ok, sr=sr, ldf=L), [({}, _native.FSEM_ERATE)])
 
 
 def test_entries_are_declared_and_bound():

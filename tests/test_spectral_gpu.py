@@ -3,6 +3,7 @@ statement of the definitions (tests/spectral_cases.py): parity at both rates, fr
 edges, a long row through the radix select, a level gap, silent frames, non-finite rows, layouts,
 `lengths`, batch and position invariance, the documented reduction, devices= and the CPU mode."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -12,18 +13,12 @@ from fast_speech_enhancement_metrics_amd import SpectralMeasures, _native
 
 from . import sdr_cases as sc
 from . import spectral_cases as sp
+from . import contract
+from . import pair_metrics as pm
 
 pytestmark = pytest.mark.gpu
 KEYS = SpectralMeasures.KEYS
-
-
-def _bits(ts):
-    return [t.cpu().numpy().view(np.uint32) for t in ts]
-
-
-def assert_bitwise(got, want, what=""):
-    for name, g, w in zip(KEYS + ("frames",), _bits(got), _bits(want)):
-        np.testing.assert_array_equal(g, w, err_msg=f"{what} {name}")
+assert_bitwise = functools.partial(contract.assert_bitwise, names=KEYS + ("frames",))
 
 
 @pytest.fixture(scope="module", params=[8000, 16000])
@@ -128,15 +123,7 @@ def test_silent_frames(rows):
 
 
 def test_nonfinite_rows(rows):
-    sr, c, n, _, m = rows
-    c2, n2 = c.clone(), n.clone()
-    n2[1, 5000] = float("nan")
-    c2[2, c.shape[1] - 1] = float("inf")  # in the tail that no frame covers
-    assert sp.frames_of(c.shape[1], sr) == sp.frames_of(c.shape[1] - 1, sr)
-    base, got = m.scores(c.cuda(), n.cuda()), m.scores(c2.cuda(), n2.cuda())
-    for g in got:
-        assert torch.isnan(g[[1, 2]]).all()
-    assert_bitwise([g[[0, 3]] for g in got], [b[[0, 3]] for b in base], "finite rows beside non-finite ones")
+    pm.nonfinite_rows(f"Spectral-{rows[0]}")
 
 
 def _call(lib, c, n, sr, ldf=None, lengths=None):
@@ -171,11 +158,7 @@ def test_layouts(rows):
     out, frames = _call(lib, wide_c[:, 1:L + 1], wide_n[:, 1:L + 1], sr, ldf=F + 5)
     assert_bitwise(list(out) + [frames[:, :, :F]], base, "ldf > F")
     assert (frames[:, :, F:] == -7.0).all()  # nothing written past the frames
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        s = m.scores(cg[:, :L], ng[:, :L], return_frames=True)
-    side.synchronize()
+    s = contract.on_side_stream(lambda: m.scores(cg[:, :L], ng[:, :L], return_frames=True))
     assert_bitwise(s, base, "side stream")
 
 
@@ -211,37 +194,11 @@ def test_scores_are_the_documented_reduction_of_the_frames(rows):
 
 
 def test_devices_fan_out_and_drop_in(rows):
-    sr, c, n, _, m = rows
-    m2 = SpectralMeasures(sr, use_gpu=True, devices=[0, 0])
-    cg, ng = c.cuda(), n.cuda()
-    assert_bitwise(m2.scores(cg, ng), m.scores(cg, ng), "devices=[0, 0]")
-    lens = [c.shape[1], 3000, c.shape[1] - 1, 4 * sc.hop_win(sr)[0] - 1]
-    one = m.scores(cg, ng, lengths=lens)
-    assert_bitwise(m2.scores(cg, ng, lengths=lens), one, "devices=[0, 0] with lengths")
-    assert_bitwise(m2.scores(cg, ng, lengths=lens, return_frames=True),
-                   m.scores(cg, ng, lengths=lens, return_frames=True), "devices=[0, 0] with frames")
-    host = [v.cpu().numpy() for v in one]
-    for metric in (m, m2):
-        res = metric(cg, ng, lengths=lens)
-        assert [tuple(r) for r in res] == [KEYS] * 4
-        for b, r in enumerate(res):
-            for k, key in enumerate(KEYS):
-                np.testing.assert_array_equal(np.float32(r[key]), host[k][b])
-    # lists of utterances
-    res = m([c[b, :k].cuda() for b, k in enumerate(lens)], [n[b, :k].cuda() for b, k in enumerate(lens)])
-    for b, r in enumerate(res):
-        for k, key in enumerate(KEYS):
-            np.testing.assert_array_equal(np.float32(r[key]), host[k][b])
+    pm.devices_fan_out(f"Spectral-{rows[0]}")
 
 
 def test_cpu_mode_agrees(rows):
-    sr, c, n, want, m = rows
-    cpu = sp.to_np(SpectralMeasures(sr, use_gpu=False).scores(c, n))
-    gpu = sp.to_np(m.scores(c.cuda(), n.cuda()))
-    for k, name in enumerate(KEYS):
-        err = float(np.abs(cpu[k] - gpu[k]).max())
-        print(f"gpu vs cpu mode {sr} {name}: worst difference {err:.3e}")
-        assert err <= sp.ATOL[name], (name, cpu[k], gpu[k])
+    pm.cpu_mode_agrees(f"Spectral-{rows[0]}")
 
 
 def test_abi_on_the_device():

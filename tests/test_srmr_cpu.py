@@ -5,8 +5,6 @@ and SRMRpy's Hilbert-envelope form."""
 import ctypes
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import torch
 
 from fast_speech_enhancement_metrics_amd import SRMR, _build, _cpu, _native
 
+from . import contract
 from . import srmr_cases as sc
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -24,20 +23,11 @@ HILBERT_LARGEST = 6.232e-3
 
 @pytest.fixture(scope="module")
 def lib():
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 def test_entries_are_declared_exported_and_bound(lib):
-    header = open(os.path.join(REPO, "include", "fsem.h")).read()
-    out = subprocess.run(["nm", "-D", "--defined-only", _build.LIB], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (fsem_[a-z0-9_]+)", out))
-    for name in ("fsem_srmr_channels", "fsem_srmr_f32"):
-        assert name in _native.SIGNATURES and f"{name}(" in header and name in exported
-        fn = getattr(lib, name)
-        assert fn.restype is _native.SIGNATURES[name][0] and fn.argtypes == _native.SIGNATURES[name][1]
-    assert ctypes.c_size_t not in _native.SIGNATURES["fsem_srmr_f32"][1]  # no workspace
-    assert lib.fsem_version() == 11  # (entries without a workspace join without a bump)
+    contract.entries_are_declared_exported_and_bound(lib, "fsem_srmr_", ("fsem_srmr_channels", "fsem_srmr_f32"))
     assert "srmr.hip" in _build.SOURCES
     assert [lib.fsem_srmr_channels(sr) for sr in (8000, 16000, 0, 4000, 11025, 22050, 44100, 48000)] == \
         [23, 23, 0, 0, 0, 0, 0, 0]
@@ -47,27 +37,18 @@ def test_entries_are_declared_exported_and_bound(lib):
 def test_abi_refuses_before_launch(lib):
     # (no GPU here: a launch would come back as FSEM_ELAUNCH; dummy non-null pointers are never read)
     p, null = ctypes.c_void_p(16), None
-    B, L = 3, 8000
+    B, L, big = 3, 8000, (1 << 29) + 1
+    call = contract.by_name(lib.fsem_srmr_f32, "deg batch length ld lengths sr energies srmr", null)
+    ok = dict(deg=p, batch=B, length=L, ld=L, lengths=null, energies=p, srmr=p)
     for sr in (8000, 16000):
-        ok = dict(deg=p, batch=B, length=L, ld=L, lengths=null, sr=sr, energies=p, srmr=p)
-
-        def call(**kw):
-            a = {**ok, **kw}
-            return lib.fsem_srmr_f32(a["deg"], a["batch"], a["length"], a["ld"], a["lengths"], a["sr"], a["energies"],
-                                     a["srmr"], null)
-
-        for name in ("deg", "energies", "srmr"):
-            assert call(**{name: null}) == _native.FSEM_EINVAL, name
-        assert call(batch=-1) == _native.FSEM_EINVAL
-        assert call(length=-1) == _native.FSEM_EINVAL
-        assert call(ld=L - 1) == _native.FSEM_EINVAL
-        big = (1 << 29) + 1
-        assert call(length=big, ld=big) == _native.FSEM_EINVAL
-        assert call(batch=0) == _native.FSEM_OK  # nothing to score, nothing launched
-        assert call(batch=0, length=0, ld=0) == _native.FSEM_OK
+        contract.refusals(call, dict(ok, sr=sr), contract.nulled(_native.FSEM_EINVAL, "deg energies srmr")
+                          + contract.each(_native.FSEM_EINVAL, dict(batch=-1), dict(length=-1), dict(ld=L - 1),
+                                          dict(length=big, ld=big))
+                          # nothing to score, nothing launched
+                          + contract.each(_native.FSEM_OK, dict(batch=0), dict(batch=0, length=0, ld=0)))
     for sr in (0, 4000, 11025, 22050, 44100, 48000):
-        assert lib.fsem_srmr_f32(p, B, L, L, null, sr, p, p, null) == _native.FSEM_ERATE, sr
-        assert lib.fsem_srmr_f32(null, B, L, L, null, sr, p, p, null) == _native.FSEM_EINVAL  # (arguments first)
+        contract.refusals(call, dict(ok, sr=sr), [({}, _native.FSEM_ERATE),
+                                                  (dict(deg=null), _native.FSEM_EINVAL)])  # (arguments first)
 
 
 @pytest.mark.parametrize("sr", [8000, 16000])

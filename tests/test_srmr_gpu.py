@@ -14,18 +14,9 @@ import torch
 from fast_speech_enhancement_metrics_amd import SRMR, _native
 
 from . import srmr_cases as sc
+from .contract import assert_bitwise, bits, on_side_stream
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous().numpy()
-    return t.view(np.uint32 if t.dtype == np.float32 else np.uint64)
-
-
-def assert_bitwise(got, want, what=""):
-    for name, g, w in zip(("SRMR", "energies"), got, want):
-        np.testing.assert_array_equal(bits(g), bits(w), err_msg=f"{what} {name}")
 
 
 @pytest.fixture(scope="module", params=[8000, 16000])
@@ -120,11 +111,7 @@ def test_layouts_positions_and_streams(rows):
     got_p = m.scores(x.cuda()[perm], lengths=[lens[j] for j in perm], return_energies=True)
     assert_bitwise(got_p, (got[0][perm], got[1][perm]), "rows permuted")
     # a side stream
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        s_side = m.scores(strided, lengths=lens_d, return_energies=True)
-    side.synchronize()
+    s_side = on_side_stream(lambda: m.scores(strided, lengths=lens_d, return_energies=True))
     assert_bitwise(s_side, got, "side stream")
 
 

@@ -15,14 +15,14 @@ import pytest
 import torch
 
 from tests.conftest import PESQ_CASES, load_golden
+from tests import contract
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
+    return contract.device()
 
 
 @pytest.mark.parametrize("name", PESQ_CASES)

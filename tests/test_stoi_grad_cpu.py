@@ -9,8 +9,6 @@ here, the quotient is within 4.5e-6 of <g, d> (relative) at that step and within
 halving moves it by less than FD_BAR = 1e-5, the bar of the check."""
 import ctypes
 import os
-import re
-import subprocess
 import warnings
 
 import numpy as np
@@ -19,6 +17,7 @@ import torch
 
 from fast_speech_enhancement_metrics_amd import STOI, _build, _cpu, _native
 
+from . import contract
 from . import stoi_grad_cases as gc
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -28,25 +27,13 @@ NAMES = [s[0] for s in gc.SETS]
 
 @pytest.fixture(scope="module")
 def lib():
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 def test_entries_are_declared_exported_and_bound(lib):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "fsem.h")).read(), flags=re.S)
-    out = subprocess.run(["nm", "-D", "--defined-only", _build.LIB], capture_output=True, text=True, check=True).stdout
-    exported = {n for n in re.findall(r" T (fsem_stoi_[a-z0-9_]+)", out)}
-    declared = set(re.findall(r"\b(fsem_stoi_[a-z0-9_]+)\s*\(", header))
-    bound = {n for n in _native.SIGNATURES if n.startswith("fsem_stoi_")}
     old = {"fsem_stoi_workspace_bytes", "fsem_stoi_f32", "fsem_stoi_tob_f32"}
-    assert exported == declared == bound == set(ENTRIES) | old
-    for name in ENTRIES:
-        fn = getattr(lib, name)
-        assert fn.restype is _native.SIGNATURES[name][0] and fn.argtypes == _native.SIGNATURES[name][1]
-        assert ctypes.c_size_t not in _native.SIGNATURES[name][1] and not name.endswith("_workspace_bytes")
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, header)
-        assert "size_t" not in m.group(1) and m.group(1).count(",") + 1 == len(_native.SIGNATURES[name][1])
-    assert "stoi_grad.hip" in _build.SOURCES and "fsem_stoi.h" in _build.HEADERS and lib.fsem_version() == 11
+    contract.entries_are_declared_exported_and_bound(lib, "fsem_stoi_", ENTRIES, old)
+    assert "stoi_grad.hip" in _build.SOURCES and "fsem_stoi.h" in _build.HEADERS
 
 
 def test_state_floats(lib):
@@ -65,35 +52,21 @@ def test_abi_refuses_before_launch(lib):
     # (no GPU here: a launch would come back as FSEM_ELAUNCH; dummy non-null pointers are never read)
     p, null = ctypes.c_void_p(256), None
     big = (1 << 29) + 4
+    EINVAL, ERATE, OK = _native.FSEM_EINVAL, _native.FSEM_ERATE, _native.FSEM_OK
     shapes = (dict(batch=-1), dict(length=0), dict(length=-4), dict(ld=15999), dict(length=big, ld=big))
+    fwd = contract.by_name(lib.fsem_stoi_state_f32, "ref deg batch length ld lengths sr s e seg state", null)
     ok = dict(ref=p, deg=p, batch=3, length=16000, ld=16000, lengths=null, sr=16000, s=p, e=p, seg=p, state=p)
-
-    def fwd(**kw):
-        a = {**ok, **kw}
-        return lib.fsem_stoi_state_f32(a["ref"], a["deg"], a["batch"], a["length"], a["ld"], a["lengths"], a["sr"],
-                                       a["s"], a["e"], a["seg"], a["state"], null)
-
-    for name in ("ref", "deg", "s", "e", "state"):
-        assert fwd(**{name: null}) == _native.FSEM_EINVAL, name
-    for kw in shapes:
-        assert fwd(**kw) == _native.FSEM_EINVAL, kw
-    assert fwd(sr=44101) == _native.FSEM_ERATE and fwd(sr=0) == _native.FSEM_ERATE
-    for kw in (dict(), dict(lengths=p), dict(seg=null), dict(sr=10000), dict(sr=48000)):
-        assert fwd(batch=0, **kw) == _native.FSEM_OK, kw  # nothing launched
+    contract.refusals(fwd, ok, contract.nulled(EINVAL, "ref deg s e state") + contract.each(EINVAL, *shapes)
+                      + contract.each(ERATE, dict(sr=44101), dict(sr=0)))
+    contract.refusals(fwd, dict(ok, batch=0), contract.each(  # nothing launched
+        OK, dict(), dict(lengths=p), dict(seg=null), dict(sr=10000), dict(sr=48000)))
+    bwd = contract.by_name(lib.fsem_stoi_grad_f32, "deg batch length ld lengths sr state gs ge grad grad_ld", null)
     okg = dict(deg=p, batch=3, length=16000, ld=16000, lengths=null, sr=16000, state=p, gs=p, ge=p, grad=p,
                grad_ld=16000)
-
-    def bwd(**kw):
-        a = {**okg, **kw}
-        return lib.fsem_stoi_grad_f32(a["deg"], a["batch"], a["length"], a["ld"], a["lengths"], a["sr"], a["state"],
-                                      a["gs"], a["ge"], a["grad"], a["grad_ld"], null)
-
-    for name in ("deg", "state", "gs", "ge", "grad"):
-        assert bwd(**{name: null}) == _native.FSEM_EINVAL, name
-    for kw in shapes + (dict(grad_ld=15999),):
-        assert bwd(**kw) == _native.FSEM_EINVAL, kw
-    assert bwd(sr=44101) == _native.FSEM_ERATE and bwd(sr=0) == _native.FSEM_ERATE
-    assert bwd(batch=0) == _native.FSEM_OK and bwd(batch=0, lengths=p, sr=8000) == _native.FSEM_OK
+    contract.refusals(bwd, okg, contract.nulled(EINVAL, "deg state gs ge grad")
+                      + contract.each(EINVAL, *shapes, dict(grad_ld=15999))
+                      + contract.each(ERATE, dict(sr=44101), dict(sr=0))
+                      + contract.each(OK, dict(batch=0), dict(batch=0, lengths=p, sr=8000)))
 
 
 def test_case_shapes():

@@ -18,14 +18,11 @@ import torch
 from fast_speech_enhancement_metrics_amd import STOI, _native
 
 from . import stoi_grad_cases as gc
+from .contract import bits
 
 pytestmark = pytest.mark.gpu
 NAMES = [s[0] for s in gc.SETS] + [gc.LONG[0], "zero", "odd"]
 LR = 3e-4   # Adam's step, 0.3 ... 0.6 % of the rows' RMS: on the float64 CPU path ESTOI rises by 0.09 ... 0.23 per row
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
 
 
 def engine(c, n, sr, lengths=None, g=None):
@@ -57,8 +54,8 @@ def test_forward_is_scores_bitwise(name):
     s, e, _, _ = engine_set(name, "random")
     s0, e0 = STOI(sr, use_gpu=True).scores(c.cuda(), n.cuda(), sr)
     assert s0.grad_fn is None and not s0.requires_grad
-    np.testing.assert_array_equal(_bits(s), _bits(s0))
-    np.testing.assert_array_equal(_bits(e), _bits(e0))
+    np.testing.assert_array_equal(bits(s), bits(s0))
+    np.testing.assert_array_equal(bits(e), bits(e0))
     want = gc.expected(name)["scores"]
     np.testing.assert_allclose(torch.stack([s, e], 1).cpu().numpy(), want, rtol=0, atol=3e-6, equal_nan=True)
 
@@ -88,7 +85,7 @@ def test_a_non_finite_sample_zeroes_its_row_only():
     bad[1, 5000] = float("nan")
     _, _, grad = engine(c, bad, sr, g=g)
     assert (grad[1] == 0).all()
-    np.testing.assert_array_equal(_bits(grad[[0, 2, 3]]), _bits(base[[0, 2, 3]]))
+    np.testing.assert_array_equal(bits(grad[[0, 2, 3]]), bits(base[[0, 2, 3]]))
     bad[1, 5000] = float("inf")
     assert (engine(c, bad, sr, g=g)[2][1] == 0).all()
 
@@ -105,28 +102,28 @@ def test_ragged_rows():
         assert (grad[b, nb:] == 0).all()
         # the unpadded row scored alone
         s1, e1, g1 = engine(c[b:b + 1, :nb], n[b:b + 1, :nb], sr, g=(g[0][b:b + 1], g[1][b:b + 1]))
-        np.testing.assert_array_equal(_bits(s1), _bits(s[b:b + 1]))
+        np.testing.assert_array_equal(bits(s1), bits(s[b:b + 1]))
         scale = float(g1.abs().max())
         assert float((g1[0] - grad[b, :nb]).abs().max()) <= gc.bar() * scale
     assert torch.isnan(s[3]) and (grad[3] == 0).all() and float(grad[1].abs().max()) > 0
     # the padding is never looked at
     c2, n2 = c.clone(), n.clone()
     c2[1, lens[1]:], n2[1, lens[1]:] = float("nan"), float("inf")
-    np.testing.assert_array_equal(_bits(engine(c2, n2, sr, lengths=lens, g=g)[2]), _bits(grad))
+    np.testing.assert_array_equal(bits(engine(c2, n2, sr, lengths=lens, g=g)[2]), bits(grad))
 
 
 def test_reproducible_and_batch_independent():
     c, n, sr = gc.rows("16k")
     _, _, base, g = engine_set("16k", "random")
-    np.testing.assert_array_equal(_bits(engine(c, n, sr, g=g)[2]), _bits(base))
+    np.testing.assert_array_equal(bits(engine(c, n, sr, g=g)[2]), bits(base))
     for b in (1, 3):
         alone = engine(c[b:b + 1], n[b:b + 1], sr, g=(g[0][b:b + 1], g[1][b:b + 1]))[2]
-        np.testing.assert_array_equal(_bits(alone[0]), _bits(base[b]))
+        np.testing.assert_array_equal(bits(alone[0]), bits(base[b]))
     # the long row alone and as row 1 of a batch of two (other segment waves, other workgroups)
     c, n, sr = gc.rows(gc.LONG[0])
     _, _, base, g = engine_set(gc.LONG[0], "random")
     two = engine(torch.cat([c, c]), torch.cat([n * 0.5, n]), sr, g=(g[0].repeat(2), g[1].repeat(2)))[2]
-    np.testing.assert_array_equal(_bits(two[1]), _bits(base[0]))
+    np.testing.assert_array_equal(bits(two[1]), bits(base[0]))
 
 
 def test_row_layouts():
@@ -138,14 +135,14 @@ def test_row_layouts():
     est = wide.requires_grad_(True)
     s, e = m.differentiable_scores(cwide[:, 12:16012], est[:, 12:16012], sr)   # slices: the engine reads them in place
     torch.autograd.backward([s, e], [g[0].cuda(), g[1].cuda()])
-    np.testing.assert_array_equal(_bits(est.grad[:, 12:16012]), _bits(base))
+    np.testing.assert_array_equal(bits(est.grad[:, 12:16012]), bits(base))
     assert (est.grad[:, :12] == 0).all() and (est.grad[:, 16012:] == 0).all()
     # an odd length against its zero-padded copy with lengths
     c, n, sr = gc.rows("odd")
     _, _, odd, g = engine_set("odd", "random")
     pad = torch.nn.functional.pad
     padded = engine(pad(c, (0, 3)), pad(n, (0, 3)), sr, lengths=[gc.ODD_LENGTH] * 4, g=g)[2]
-    np.testing.assert_array_equal(_bits(padded[:, :gc.ODD_LENGTH]), _bits(odd))
+    np.testing.assert_array_equal(bits(padded[:, :gc.ODD_LENGTH]), bits(odd))
     # half precision estimates: cast to float32, the gradient back in their dtype
     half = n.cuda().to(torch.bfloat16).requires_grad_(True)
     m.loss(c.cuda(), half, sr).backward()
@@ -212,12 +209,12 @@ def test_c_entries_directly():
     assert lib.fsem_stoi_state_f32(p(cd), p(nd), B, L, ld, None, sr, p(s), p(e), p(seg), p(state), st) == _native.FSEM_OK
     assert seg.tolist() == gc.segments("8k")
     s0, e0, base, g = engine_set("8k", "random")
-    np.testing.assert_array_equal(_bits(s), _bits(s0))
-    np.testing.assert_array_equal(_bits(e), _bits(e0))
+    np.testing.assert_array_equal(bits(s), bits(s0))
+    np.testing.assert_array_equal(bits(e), bits(e0))
     grad = torch.full((B, grad_ld), 7.0, device="cuda")
     gs, ge = g[0].cuda(), g[1].cuda()
     for _ in range(2):   # (the state may be read again)
         assert lib.fsem_stoi_grad_f32(p(nd), B, L, ld, None, sr, p(state), p(gs), p(ge), p(grad), grad_ld, st) == \
             _native.FSEM_OK
-        np.testing.assert_array_equal(_bits(grad[:, :L]), _bits(base))
+        np.testing.assert_array_equal(bits(grad[:, :L]), bits(base))
         assert (grad[:, L:] == 7.0).all()   # the padding columns are not written

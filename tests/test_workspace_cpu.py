@@ -3,7 +3,10 @@ is pinned to tests/golden/workspace_bytes.json (recorded from the library of the
 that file), and every entry that takes a workspace refuses one that is a byte short, before
 anything launches.  No GPU is needed: the library answers these on the host.
 
-    python -m tests.test_workspace_cpu        # re-record the golden file from the built library
+The libraries beside libfsem.so (LSD, BSSSDR, Composite, DNSMOS) keep one golden file each,
+tests/golden/<library>_workspace_bytes.json, on the same PAIRS.
+
+    python -m tests.test_workspace_cpu        # re-record every golden file from the built libraries
 """
 import ctypes
 import json
@@ -11,6 +14,8 @@ import os
 import subprocess
 
 import pytest
+
+from . import contract
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 GOLDEN = os.path.join(REPO, "tests", "golden", "workspace_bytes.json")
@@ -29,6 +34,46 @@ SDR_RATES = [4000, 8000, 11025, 16000, 22050, 44100, 48000, 96000, 192000]
 SDR_REFUSED = [3999, 192001]
 SDR_ALL = range(4000, 192001)
 B, L, LD = 3, 40077, 40080  # the short-workspace case (the alignment entries take ld % 4 == 0)
+OVER = (1 << 29) + 1  # a length past the engine's limit: every query answers 0
+
+
+def library_golden(name: str) -> str:
+    return os.path.join(REPO, "tests", "golden", f"{name}_workspace_bytes.json")
+
+
+def record_library(name: str, lib) -> dict:
+    """What tests/golden/<name>_workspace_bytes.json holds beside "pairs"."""
+    if name == "composite":
+        return {name: {str(sr): [lib.fsem_composite_workspace_bytes(b, l, sr) for b, l in PAIRS]
+                       for sr in (8000, 16000, 7999, 22050)}}
+    sizes = {name: [getattr(lib, f"fsem_{name}_workspace_bytes")(b, l) for b, l in PAIRS]}
+    if name == "dnsmos":
+        sizes.update(min=lib.fsem_dnsmos_min_workspace_bytes(), weights=lib.fsem_dnsmos_weights_bytes())
+    return sizes
+
+
+def _batch_and_length_limits(lib, golden, name):
+    query = getattr(lib, f"fsem_{name}_workspace_bytes")
+    assert all(golden[name][:-1]) and golden[name][-1] == 0  # (last pair: batch 0)
+    assert query(4, 0) == 0 and query(1, OVER) == 0
+
+
+def _composite_rates(lib, golden, name):
+    assert all(golden[name]["16000"][:-1]) and all(golden[name]["8000"][:-1])  # (last pair: batch 0)
+    assert not any(golden[name]["22050"]) and not any(golden[name]["7999"])
+
+
+def _dnsmos_cap(lib, golden, name):
+    """The recommended size stops growing at the cap on segments per pass."""
+    from fast_speech_enhancement_metrics_amd import _native
+    _batch_and_length_limits(lib, golden, name)
+    assert lib.fsem_dnsmos_workspace_bytes(4096, 160000) == lib.fsem_dnsmos_workspace_bytes(70000, 1 << 20)
+    assert golden["min"] < golden[name][4] <= _native.DNSMOS_MAX_PASS * golden["min"]
+
+
+# library: what its test pinned beyond the recorded sizes
+LIBRARIES = {"lsd": _batch_and_length_limits, "bsssdr": _batch_and_length_limits, "composite": _composite_rates,
+             "dnsmos": _dnsmos_cap}
 
 
 def record(lib) -> dict:
@@ -48,9 +93,7 @@ def record(lib) -> dict:
 
 @pytest.fixture(scope="module")
 def lib():
-    from fast_speech_enhancement_metrics_amd import _build, _native
-    _build.build()
-    return _native.load()
+    return contract.load_lib()
 
 
 @pytest.fixture(scope="module")
@@ -90,6 +133,18 @@ def test_workspace_sizes_equal_the_recorded_ones(lib, golden):
     for sr in SDR_ALL:
         g = lib.fsem_sdr_workspace_bytes(B, L, sr)
         assert g in (want_of[sr], up256(want_of[sr])), (sr, g, want_of[sr])
+
+
+@pytest.mark.parametrize("name", list(LIBRARIES))
+def test_library_workspace_sizes_equal_the_recorded_ones(lib, name):
+    from fast_speech_enhancement_metrics_amd import _native
+    other = getattr(_native, f"load_{name}")()
+    with open(library_golden(name)) as f:
+        golden = json.load(f)
+    assert golden["pairs"] == [list(p) for p in PAIRS]
+    got = record_library(name, other)
+    assert got == {k: golden[k] for k in got}
+    LIBRARIES[name](other, golden, name)
 
 
 def short_workspace_calls(lib):
@@ -158,3 +213,9 @@ if __name__ == "__main__":
         json.dump(out, f, separators=(",", ":"))
         f.write("\n")
     print("wrote", GOLDEN)
+    for name in LIBRARIES:
+        with open(library_golden(name), "w") as f:
+            sizes = record_library(name, getattr(_native, f"load_{name}")())
+            json.dump({"pairs": [list(p) for p in PAIRS], **sizes}, f, separators=(",", ":"))
+            f.write("\n")
+        print("wrote", library_golden(name))
