@@ -9,8 +9,7 @@
 //      (P.862 crude_align);
 //   3. ta_fine_fft + ta_fine_pick: within +-383 samples of the crude delay, the lag of the
 //      largest cross-correlation of the signals' first differences, over the whole row (the
-//      partials per 5120-sample chunk by fast correlation; ta_fine_partial, the direct form, is
-//      kept for A/B behind FSEM_FINE_FFT=0, see launch_fine);
+//      partials per 5120-sample chunk by fast correlation);
 //   4. ta_shift: the aligned degraded row a[n] = deg[n + D] (0 <= n + D < L_row), else 0.
 // Delay D > 0: the degraded row lags the clean one, deg[n] ~ ref[n - D].
 // Utterance mode (fsem_time_align_utt_f32, P.862 sections 10.3-10.5 as restated in the oracle):
@@ -19,11 +18,12 @@
 //      the regions' 5120-sample pieces;
 //   6. ta_crude_utt: each utterance's envelope lag over its search window (+-300 ms around it),
 //      within +-75 frames of the row's crude lag;
-//   7. ta_fine_fft (utterance pieces; launch_fine as in stage 3): the first-difference
-//      correlation per piece around the utterance's crude delay;
+//   7. ta_fine_fft (utterance pieces): the first-difference correlation per piece around the
+//      utterance's crude delay;
 //   8. ta_pick_utt: each region's fine delay, or two delays when splitting it at a piece boundary
 //      raises the summed correlation peak by 20 % and the halves' delays differ by >= 16 samples;
-//      ta_segments: the row's segments (equal neighbours merged) and its longest segment's delay;
+//      ta_segments: the row's segments (equal neighbours merged, at most MAXSEG) and its longest
+//      segment's delay;
 //   9. ta_shift_seg: a[n] = deg[n + D_k] in segment k.
 //
 // P.862 mode (fsem_time_align_p862_f32, oracle/align_oracle.py steps 10-12; P.862 sections
@@ -35,11 +35,10 @@
 //      range splits at the piece boundary whose two halves (two or more votes each, delays >= 1 ms
 //      apart) are both more confident than the whole, the most confident pair first, and each
 //      half once more (P.862 utterance_split, two levels: up to 4 segments per utterance);
-//      ta_segments_p862: the row's segments as in stage 8, at most MAXSEG.
-// Cost was set by stage 3: 767 lags x L multiply-adds per row (about 123 M for 10 s) as
-// register-blocked packed FMAs out of LDS in the direct form (ta_fine_partial); the default
-// ta_fine_fft computes the same partials by fast correlation (per 1280-sample block, 2048-point
-// transforms: ~12x less work).
+//      ta_segments: the row's segments as in stage 8.
+// Cost is set by stage 3: 767 lags x L multiply-adds per row (about 123 M for 10 s) if summed
+// directly; ta_fine_fft computes the partials by fast correlation (per 1280-sample block,
+// 2048-point transforms: ~12x less work).
 // The other stages are O(L) or O(M * L / 64).
 #include "fsem_common.h"
 #include "fsem_fft.h"
@@ -52,13 +51,11 @@ constexpr int FRAME = 64;            // envelope frame (4 ms at 16 kHz)
 constexpr int VAD_ITERS = 12;
 constexpr int FINE = 383;            // fine half-width in samples
 constexpr int NLAG = 2 * FINE + 1;   // 767
-constexpr int LG = 32;               // lags per lane
-constexpr int NGRP = 24;             // lag groups (24 x 32 = 768 slots >= NLAG)
-constexpr int NSL = 10;              // sample slices per chunk
-constexpr int SL = 512;              // samples per slice
-constexpr int CS = NSL * SL;         // samples per chunk (5120)
-constexpr int WIN = CS + NGRP * LG;  // degraded window per chunk (5888)
-static_assert(NGRP * LG >= NLAG && NGRP * NSL <= 256, "fine-stage thread map");
+constexpr int FB = 1280;             // samples per block of the fine stage (one wave's transforms)
+constexpr int FN = 2048;             // its transform length
+constexpr int CS = 4 * FB;           // samples per chunk (5120): a workgroup's four blocks
+constexpr int PART_LD = 768;         // row stride of the partials: a slot's NLAG lags, padded
+static_assert(PART_LD >= NLAG && FB + PART_LD - 1 <= FN, "a slot's lags fit its row; no wrap in the transform");
 constexpr int ENV_LDS = 6144;        // envelope frames per signal kept in LDS by ta_crude
 // utterance mode (oracle/align_oracle.py steps 5-9; P.862 constant names)
 constexpr int MINSPEECH = 4;         // frames: shorter speech runs are discarded (MINSPEECHLGTH)
@@ -70,9 +67,58 @@ constexpr int MAXSEG = 2 * MAXU;     // segments per row (include/fsem.h FSEM_AL
 constexpr int SPLIT_MIN = 16;        // samples: least delay difference of a split
 constexpr double SPLIT_GAIN = 1.2;   // least gain of the summed correlation peaks of a split
 
-// LDS index of the degraded window's element m: a one-float skew every 32 so the 24 lag groups
-// of a wave (32 floats apart) read distinct banks.
-__device__ __forceinline__ int skew(int m) { return m + (m >> 5); }
+// First-maximum argmax over a 256-thread workgroup: (v, j) with v > 0, or (0, INT32_MAX).
+__device__ __forceinline__ void block_argmax(double &v, int &j, double *sv, int *sj) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double v2 = __shfl_xor(v, off, 64);
+    const int j2 = __shfl_xor(j, off, 64);
+    if (v2 > v || (v2 == v && j2 < j)) {
+      v = v2;
+      j = j2;
+    }
+  }
+  const int w = threadIdx.x >> 6;
+  __syncthreads();  // the previous call's readers are done
+  if ((threadIdx.x & 63) == 0) {
+    sv[w] = v;
+    sj[w] = j;
+  }
+  __syncthreads();
+  v = sv[0];
+  j = sj[0];
+#pragma unroll
+  for (int q = 1; q < 4; ++q)
+    if (sv[q] > v || (sv[q] == v && sj[q] < j)) {
+      v = sv[q];
+      j = sj[q];
+    }
+}
+
+// The fine stage's partials, part[slot][PART_LD]: thread tid holds the lags l = tid + 256 q
+// (q < 3, l < NLAG).  Pieces [0, m) of P added onto t, per lag in piece order (double).
+__device__ __forceinline__ void add_pieces(const float *__restrict__ P, int m, int tid, double (&t)[3]) {
+  for (int i = 0; i < m; ++i)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const int l = tid + 256 * q;
+      if (l < NLAG) t[q] += P[i * PART_LD + l];
+    }
+}
+// The thread's first peak above zero of such sums (its lags ascending): (value, lag index), or
+// (0, INT32_MAX) -- a block_argmax operand.
+__device__ __forceinline__ void first_peak(const double (&t)[3], int tid, double &v, int &j) {
+  v = 0.0;
+  j = INT32_MAX;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const int l = tid + 256 * q;
+    if (l < NLAG && t[q] > v) {
+      v = t[q];
+      j = l;
+    }
+  }
+}
 
 // ---------------------------------------------------------------- stage 1: frame energies
 // 16 lanes per frame (one float4 each), 4 frames per wave; frames of row s: k < L_row / 64.
@@ -151,10 +197,10 @@ __global__ void __launch_bounds__(256) ta_crude(int64_t B, int64_t L, const int3
                                                 const float *__restrict__ E, int64_t nfr_cap, int max_frames,
                                                 int *__restrict__ crude) {
   __shared__ float er[ENV_LDS], ed[ENV_LDS];
-  __shared__ float bv[256];
-  __shared__ int bj[256];
+  __shared__ double sv[4];
+  __shared__ int sj[4];
   const int64_t b = grid_row_xy();
-  if (b >= B) return;
+  if (b >= B) return;  // uniform
   const int nfr = (int)(row_length(lengths, b, L) / FRAME);
   const int tid = threadIdx.x;
   const float *gr = E + b * nfr_cap, *gd = E + (B + b) * nfr_cap;
@@ -186,39 +232,22 @@ __global__ void __launch_bounds__(256) ta_crude(int64_t B, int64_t L, const int3
       arg = j;
     }
   }
-  bv[tid] = best;
-  bj[tid] = (best > 0.f) ? arg : INT32_MAX;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) {
-      const float v2 = bv[tid + off];
-      const int j2 = bj[tid + off];
-      if (v2 > bv[tid] || (v2 == bv[tid] && j2 < bj[tid])) {
-        bv[tid] = v2;
-        bj[tid] = j2;
-      }
-    }
-    __syncthreads();
-  }
-  if (tid == 0) crude[b] = (bj[0] == INT32_MAX) ? 0 : FRAME * bj[0];
+  double v = best;  // (a float converts exactly)
+  int jb = (best > 0.f) ? arg : INT32_MAX;
+  block_argmax(v, jb, sv, sj);
+  if (tid == 0) crude[b] = (jb == INT32_MAX) ? 0 : FRAME * jb;
 }
 
 // ---------------------------------------------------------------- stage 3: fine partials
-// Workgroup (row b, chunk c): samples n in [c CS, (c+1) CS).  First differences in LDS:
-// wr[n] (n >= 1, n < L_row), wd[m] for m = n + D over the window D in [D0 - FINE, D0 - FINE + 768).
-// Thread (slice sl < NSL, group g < NGRP; 240 of the 256 lanes): LG = 32 lags
-// D0 - FINE + LG g + i over its SL = 512 samples, the window wd[n + lag0 + i] held in registers
-// as even- and odd-aligned pairs, two samples per step.  Partials per lag over the chunk: the
-// NSL = 10 slices added in order, to part[b][c][768].
-// Static LDS: wr (20 KB) + wd (24 KB) + ps (30 KB) = 74 KB per workgroup -- above the 64 KB
-// of earlier CDNA parts; gfx950's 160 KB LDS per CU holds two such workgroups.
-constexpr size_t kFineLds = sizeof(float) * (CS + (WIN + WIN / 32 + 64) + NSL * NGRP * LG);
-static_assert(kFineLds <= 80 * 1024, "ta_fine_partial: two workgroups per CU in gfx950's 160 KB of LDS");
-// Utterance mode (utt != nullptr): slot c of row b is piece i of utterance u (pieces of u are
-// slots [cs[u], cs[u+1])): samples [reg[u] + i CS, min(reg[u] + (i+1) CS, reg[u+1])) at lags
-// around that utterance's crude delay (ucrude[u]).
-// Bad-interval realignment (desc != nullptr): slot c < ndesc[b] of row b is desc[b][c] = {first
-// sample, end sample, centre lag, interval}.
+// A workgroup takes one slot: up to CS samples of a row's reference, correlated (first
+// differences of both signals, 0 outside [1, L_row)) with the degraded row at the PART_LD lags
+// from lag0 = centre - FINE on, to part[b][c][PART_LD].  What slot c of row b is:
+// Row mode (no tables): chunk c, samples [c CS, (c+1) CS), around the row's crude delay.
+// Utterance mode (nutt != nullptr): piece i of utterance u (pieces of u are slots
+// [cs[u], cs[u+1])): samples [reg[u] + i CS, min(reg[u] + (i+1) CS, reg[u+1])) around that
+// utterance's crude delay (ucrude[u]).
+// Bad-interval realignment (desc != nullptr): slot c < ndesc[b] is desc[b][c] = {first sample,
+// end sample, centre lag, interval}.
 struct UttTables {
   const int *nutt;    // [B]
   const int *reg;     // [B][MAXU + 1] region starts (samples)
@@ -227,7 +256,7 @@ struct UttTables {
   const int4 *desc = nullptr;
   const int *ndesc = nullptr;  // [B]
 };
-// Workgroup blk's slot: row b, slot c, samples [n0, hi) correlated at lags lag0 + j (j < 768).
+// Workgroup blk's slot: row b, slot c, samples [n0, hi) correlated at lags lag0 + j (j < PART_LD).
 struct SlotRange {
   bool valid;
   int64_t b, Lr, n0, hi, lag0;
@@ -272,91 +301,20 @@ __device__ __forceinline__ SlotRange slot_range(int64_t blk, int64_t B, int64_t 
   return r;
 }
 
-__global__ void __launch_bounds__(256) ta_fine_partial(const float *__restrict__ ref, const float *__restrict__ deg,
-                                                       int64_t B, int64_t L, int64_t ld,
-                                                       const int32_t *__restrict__ lengths,
-                                                       const int *__restrict__ crude, int nchunk,
-                                                       float *__restrict__ part, UttTables ut) {
-  __shared__ float wr[CS];
-  __shared__ float wd[WIN + WIN / 32 + 64];
-  __shared__ float ps[NSL][NGRP * LG];
-  const SlotRange sr = slot_range(blockIdx.x, B, L, lengths, crude, nchunk, ut);
-  if (!sr.valid) return;  // uniform
-  const int64_t b = sr.b, Lr = sr.Lr, n0 = sr.n0, hi = sr.hi, lag0 = sr.lag0;
-  const int c = sr.c;
-  const float *x = ref + b * ld, *y = deg + b * ld;
-  const int tid = threadIdx.x;
-  auto dif = [Lr](const float *z, int64_t i) {  // first difference, 0 outside [1, L_row)
-    return (i >= 1 && i < Lr) ? z[i] - z[i - 1] : 0.f;
-  };
-  for (int i = tid; i < CS; i += 256) wr[i] = (n0 + i < hi) ? dif(x, n0 + i) : 0.f;
-  for (int i = tid; i < WIN + 32; i += 256) wd[skew(i)] = dif(y, n0 + lag0 + i);  // +32: last slides
-  __syncthreads();
-  const int g = tid % NGRP, sl = tid / NGRP;
-  if (sl < NSL) {
-    // packed FP32 (v_pk_fma_f32: two lags per instruction).  W[i] = the window element of lag
-    // LG g + i at the current sample; E[p] = (W[2p], W[2p+1]) serves the even sample of a
-    // double step, O[p] = (W[2p+1], W[2p+2]) the odd one.  A double step retires the logical
-    // pair 0 of both and appends the pairs (W[LG], W[LG+1]) / (W[LG+1], W[LG+2]): physical slot
-    // (p + k) % (LG/2) holds logical pair p in double step k (unrolled: no moves but the
-    // append).  Per double step: LG packed FMAs, two window reads, half a float4 of wr.
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    constexpr int NP = LG / 2;
-    f2 acc[NP], E[NP], O[NP];
-    const int base = SL * sl + LG * g;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      acc[p] = (f2){0.f, 0.f};
-      const float a = wd[skew(base + 2 * p)], b1 = wd[skew(base + 2 * p + 1)], b2 = wd[skew(base + 2 * p + 2)];
-      E[p] = (f2){a, b1};
-      O[p] = (f2){b1, b2};
-    }
-    const float4 *rr4 = reinterpret_cast<const float4 *>(wr + SL * sl);
-    for (int n = 0; n < SL; n += LG) {
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        const int sm = n + 2 * k;
-        const float4 xq = rr4[sm >> 2];  // the same float4 for two double steps (CSE)
-        const float x0 = (k & 1) ? xq.z : xq.x, x1 = (k & 1) ? xq.w : xq.y;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) acc[p] = __builtin_elementwise_fma((f2){x0, x0}, E[(p + k) % NP], acc[p]);
-#pragma unroll
-        for (int p = 0; p < NP; ++p) acc[p] = __builtin_elementwise_fma((f2){x1, x1}, O[(p + k) % NP], acc[p]);
-        const float wa = wd[skew(base + sm + LG + 1)], wb = wd[skew(base + sm + LG + 2)];
-        E[k] = (f2){O[(NP - 1 + k) % NP].y, wa};
-        O[k] = (f2){wa, wb};
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      ps[sl][LG * g + 2 * p] = acc[p].x;
-      ps[sl][LG * g + 2 * p + 1] = acc[p].y;
-    }
-  }
-  __syncthreads();
-  for (int j = tid; j < NGRP * LG; j += 256) {
-    float t = ps[0][j];
-#pragma unroll
-    for (int q = 1; q < NSL; ++q) t += ps[q][j];
-    part[(b * nchunk + c) * (NGRP * LG) + j] = t;
-  }
-}
-
-// ---------------------------------------------------------------- stage 3, FFT form
-// The same partials as ta_fine_partial by fast correlation (FSEM_FINE_FFT): wave q of the
-// workgroup takes the slot's block q, x[i] = wr[n0 + 1280 q + i] (i < 1280 and below the slot's
-// end, else 0) and y[i] = wd[n0 + 1280 q + lag0 + i] (i < 2048); its c_q[j] = sum_i x[i] y[i + j]
-// (j < 768) is their circular correlation of length 2048 (no wrap: 1280 + 767 < 2048):
+// The partials by fast correlation.  With wr / wd the first differences of the reference and the
+// degraded row, wave q of the workgroup takes the slot's block q, x[i] = wr[n0 + 1280 q + i]
+// (i < 1280 and below the slot's end, else 0) and y[i] = wd[n0 + 1280 q + lag0 + i] (i < 2048);
+// its c_q[j] = sum_i x[i] y[i + j] (j < 768) is their circular correlation of length 2048 (no
+// wrap: 1280 + 767 < 2048):
 //   Z = FFT(x + i y) -- four 512-point transforms of the samples 4n + r (fft512_wave_x2) and a
 //   radix-4 step -- then with A = Z[k] + conj Z[-k], B = Z[k] - conj Z[-k]:
 //   X = A / 2, Y = B / 2i, and c = Re IFFT(conj(X) Y) = Re FFT(X conj(Y)) / 2048 with
 //   X conj(Y) = i A conj(B) / 4 (one more four-transform FFT, after a transposition through the
-//   wave's LDS area).  The four blocks' c_q are added in block order.  The values differ from the
-//   direct sums by float32 rounding (both forms: ~1e-7 .. 1e-6 of |x| |y|); the work per slot is
-//   ~12x smaller.
-constexpr int FB = 1280;  // samples of x per block (wave)
-constexpr int FN = 2048;  // transform length
-static_assert(4 * FB == CS && FB + NGRP * LG - 1 <= FN, "four blocks per slot; no wrap");
+//   wave's LDS area).  The four blocks' c_q are added in block order.  The values differ from
+//   direct sums by float32 rounding (either way: ~1e-7 .. 1e-6 of |x| |y|); the work per slot is
+//   ~12x smaller (4096 x 10 s PESQ with row / utterance / P.862-mode alignment: 11.2 / 13.8 /
+//   28.8 ms against 19.3 / 26.6 / 45.7 ms with the direct kernel this replaced, every synthetic
+//   delay recovered by both, profiles/r6_g/ab_fine_fft.txt).
 
 __device__ __forceinline__ cf w2048(int t) {  // exp(-2 pi i t / 2048), 0 <= t < 2048
   // W_512^(t >> 2) from the 512-point table times W_2048^(t & 3)
@@ -400,7 +358,7 @@ __global__ void __launch_bounds__(256) ta_fine_fft(const float *__restrict__ ref
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t tx = xb + i0 + r, ty = yb + i0 + r;
-        // first differences, 0 outside [1, L_row) (ta_fine_partial's dif), x also past the slot
+        // first differences, 0 outside [1, L_row), x also past the slot
         const float dx = (i0 + r < FB && tx < xend && tx >= 1 && tx < Lr) ? xv[r + 1] - xv[r] : 0.f;
         const float dy = (ty >= 1 && ty < Lr) ? yv[r + 1] - yv[r] : 0.f;
         g[r][s] = {dx, dy};
@@ -472,24 +430,8 @@ __global__ void __launch_bounds__(256) ta_fine_fft(const float *__restrict__ ref
   __syncthreads();
   const float *c0 = reinterpret_cast<const float *>(fbuf[0]), *c1 = reinterpret_cast<const float *>(fbuf[1]),
               *c2 = reinterpret_cast<const float *>(fbuf[2]), *c3 = reinterpret_cast<const float *>(fbuf[3]);
-  for (int j = tid; j < NGRP * LG; j += 256)
-    part[(sr.b * nchunk + sr.c) * (NGRP * LG) + j] = ((c0[j] + c1[j]) + c2[j]) + c3[j];
-}
-
-// the fine stage's partials of every slot: the FFT form (default), or the direct one
-// (FSEM_FINE_FFT=0, kept for A/B): 4096 x 10 s PESQ with row / utterance / P.862-mode alignment
-// 19.3 / 26.6 / 45.7 ms direct, 11.2 / 13.8 / 28.8 ms FFT, every synthetic delay recovered by both
-// (profiles/r6_g/ab_fine_fft.txt)
-#ifndef FSEM_FINE_FFT
-#define FSEM_FINE_FFT 1
-#endif
-inline void launch_fine(unsigned grid, hipStream_t st, const float *ref, const float *deg, int64_t B, int64_t L,
-                        int64_t ld, const int32_t *lengths, const int *crude, int nchunk, float *part,
-                        const UttTables &ut) {
-  if (FSEM_FINE_FFT)
-    ta_fine_fft<<<grid, 256, 0, st>>>(ref, deg, B, L, ld, lengths, crude, nchunk, part, ut);
-  else
-    ta_fine_partial<<<grid, 256, 0, st>>>(ref, deg, B, L, ld, lengths, crude, nchunk, part, ut);
+  for (int j = tid; j < PART_LD; j += 256)
+    part[(sr.b * nchunk + sr.c) * PART_LD + j] = ((c0[j] + c1[j]) + c2[j]) + c3[j];
 }
 
 // ---------------------------------------------------------------- stage 3b: fine delay
@@ -497,40 +439,41 @@ inline void launch_fine(unsigned grid, hipStream_t st, const float *ref, const f
 // maximum above zero (smallest lag), else the crude delay.
 __global__ void __launch_bounds__(256) ta_fine_pick(int64_t B, const int *__restrict__ crude, int nchunk,
                                                     const float *__restrict__ part, int *__restrict__ delay) {
-  __shared__ double bv[256];
-  __shared__ int bj[256];
+  __shared__ double sv[4];
+  __shared__ int sj[4];
   const int64_t b = grid_row_xy();
-  if (b >= B) return;
+  if (b >= B) return;  // uniform
   const int tid = threadIdx.x;
-  double best = 0.0;
-  int arg = INT32_MAX;
-  for (int j = tid; j < NLAG; j += 256) {
-    double t = 0.0;
-    for (int c = 0; c < nchunk; ++c) t += part[(b * nchunk + c) * (NGRP * LG) + j];
-    if (t > best) {
-      best = t;
-      arg = j;
-    }
-  }
-  bv[tid] = best;
-  bj[tid] = arg;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) {
-      const double v2 = bv[tid + off];
-      const int j2 = bj[tid + off];
-      if (v2 > bv[tid] || (v2 == bv[tid] && j2 < bj[tid])) {
-        bv[tid] = v2;
-        bj[tid] = j2;
-      }
-    }
-    __syncthreads();
-  }
-  if (tid == 0) delay[b] = (bj[0] == INT32_MAX) ? crude[b] : crude[b] - FINE + bj[0];
+  double t[3] = {0.0, 0.0, 0.0}, v;
+  int j;
+  add_pieces(part + b * nchunk * PART_LD, nchunk, tid, t);
+  first_peak(t, tid, v, j);
+  block_argmax(v, j, sv, sj);
+  if (tid == 0) delay[b] = (j == INT32_MAX) ? crude[b] : crude[b] - FINE + j;
 }
 
 // ---------------------------------------------------------------- stage 4: shift
-// Four outputs per thread (one float4 store; ld_out % 4 == 0), four scalar reads at n + D.
+// What the three shift kernels share.  deg[m] inside the row, else 0:
+__device__ __forceinline__ float fetch(const float *__restrict__ y, int64_t m, int64_t Lr) {
+  return (m >= 0 && m < Lr) ? y[m] : 0.f;
+}
+// A thread's four outputs at n .. n + 3 of a row of capacity L (n % 4 == 0, n < L), value(p) the
+// one at p, asked in ascending order: one float4 store (ld_out % 4 == 0), or a scalar tail.
+template <class F>
+__device__ __forceinline__ void store4(float *row, int64_t n, int64_t L, F value) {
+  float v[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = value(n + i);
+  if (n + 4 <= L) {
+    *reinterpret_cast<float4 *>(row + n) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int i = 0; i < 4 && n + i < L; ++i) row[n + i] = v[i];
+  }
+}
+// 1024 outputs per workgroup, rows in y and z.
+inline dim3 shift_grid(int64_t length, int64_t batch) { return grid_yz((unsigned)((length + 1023) / 1024), batch); }
+
+// Four scalar reads at n + D.
 __global__ void __launch_bounds__(256) ta_shift(const float *__restrict__ deg, int64_t B, int64_t L, int64_t ld,
                                                 const int32_t *__restrict__ lengths, const int *__restrict__ delay,
                                                 float *__restrict__ out, int64_t ld_out) {
@@ -541,26 +484,44 @@ __global__ void __launch_bounds__(256) ta_shift(const float *__restrict__ deg, i
   const int64_t Lr = row_length(lengths, b, L);
   const int64_t D = delay[b];
   const float *y = deg + b * ld;
-  float v[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t m = n + i + D;
-    v[i] = (n + i < Lr && m >= 0 && m < Lr) ? y[m] : 0.f;
-  }
-  if (n + 4 <= L) {
-    *reinterpret_cast<float4 *>(out + b * ld_out + n) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    for (int i = 0; i < 4 && n + i < L; ++i) out[b * ld_out + n + i] = v[i];
-  }
+  store4(out + b * ld_out, n, L, [&](int64_t p) { return p < Lr ? fetch(y, p + D, Lr) : 0.f; });
 }
 
 // ---------------------------------------------------------------- stage 5: utterances
-// One wave per row: the reference envelope 64 frames at a time (one coalesced load, a ballot of
-// the speech frames), the runs of each block walked with bit scans in wave-uniform (scalar)
-// code -- speech runs of MINSPEECH frames or more, joined across gaps < JOIN frames, kept from
-// MINUTT frames, at most MAXU (later ones join the last); then the regions (boundary: the
-// middle of the gap, in whole frames) and their pieces.  No utterance: one covering the row
-// (its crude window: every frame).
+// One wave walks the runs of a per-frame predicate over frames [0, n): 64 frames at a time (one
+// coalesced load per lane in active(k), a ballot of the active frames), the runs of each block
+// found with bit scans in wave-uniform (scalar) code, a run open at a block's end carried into
+// the next; end_run(rs, k) at the end of each run [rs, k), in order.
+template <class Active, class EndRun>
+__device__ __forceinline__ void walk_runs(int n, int lane, Active active, EndRun end_run) {
+  int rs = -1;  // the open run's first frame
+  for (int k0 = 0; k0 < n; k0 += 64) {
+    const int k = k0 + lane;
+    const uint64_t m = __ballot(k < n && active(k));
+    int pos = 0;
+    while (pos < 64) {
+      if (rs >= 0) {
+        const uint64_t z = ~m >> pos;  // the open run ends at the next inactive frame
+        if (z == 0) break;             // ... in a later block
+        pos += __builtin_ctzll(z);
+        end_run(rs, k0 + pos);
+        rs = -1;
+      } else {
+        const uint64_t o = m >> pos;
+        if (o == 0) break;
+        pos += __builtin_ctzll(o);
+        rs = k0 + pos;
+      }
+    }
+  }
+  if (rs >= 0) end_run(rs, n);
+}
+
+// One wave per row: the runs of the reference envelope's speech frames (walk_runs) -- speech
+// runs of MINSPEECH frames or more, joined across gaps < JOIN frames, kept from MINUTT frames, at
+// most MAXU (later ones join the last); then the regions (boundary: the middle of the gap, in
+// whole frames) and their pieces.  No utterance: one covering the row (its crude window: every
+// frame).
 __global__ void __launch_bounds__(64) ta_utterances(int64_t B, int64_t L, const int32_t *__restrict__ lengths,
                                                     const float *__restrict__ E, int64_t nfr_cap,
                                                     int *__restrict__ nutt, int *__restrict__ utt,
@@ -572,7 +533,7 @@ __global__ void __launch_bounds__(64) ta_utterances(int64_t B, int64_t L, const 
   const int64_t Lr = row_length(lengths, b, L);
   const int nfr = (int)(Lr / FRAME);
   const float *env = E + b * nfr_cap;
-  int n = 0, s0 = -1, e0 = -1, rs = -1;  // utterances, joined run [s0, e0), open raw run from rs
+  int n = 0, s0 = -1, e0 = -1;  // utterances, joined run [s0, e0)
   auto flush = [&]() {
     if (s0 >= 0 && e0 - s0 >= MINUTT) {
       if (n < MAXU) {
@@ -586,7 +547,7 @@ __global__ void __launch_bounds__(64) ta_utterances(int64_t B, int64_t L, const 
       }
     }
   };
-  auto close_run = [&](int k) {  // the raw run [rs, k) ends
+  auto close_run = [&](int rs, int k) {  // the raw run [rs, k) ends
     if (k - rs >= MINSPEECH) {
       if (s0 >= 0 && rs - e0 < JOIN) {
         e0 = k;
@@ -596,27 +557,8 @@ __global__ void __launch_bounds__(64) ta_utterances(int64_t B, int64_t L, const 
         e0 = k;
       }
     }
-    rs = -1;
   };
-  for (int k0 = 0; k0 < nfr; k0 += 64) {
-    const int k = k0 + lane;
-    const uint64_t m = __ballot(k < nfr && env[k] > 0.f);
-    int pos = 0;
-    while (pos < 64) {
-      if (rs >= 0) {
-        const uint64_t z = ~m >> pos;  // the open run ends at the next inactive frame
-        if (z == 0) break;             // ... in a later block
-        pos += __builtin_ctzll(z);
-        close_run(k0 + pos);
-      } else {
-        const uint64_t o = m >> pos;
-        if (o == 0) break;
-        pos += __builtin_ctzll(o);
-        rs = k0 + pos;
-      }
-    }
-  }
-  if (rs >= 0) close_run(nfr);
+  walk_runs(nfr, lane, [&](int k) { return env[k] > 0.f; }, close_run);
   flush();
   if (n == 0) {
     if (lane == 0) {
@@ -638,34 +580,6 @@ __global__ void __launch_bounds__(64) ta_utterances(int64_t B, int64_t L, const 
     c[0] = 0;
     for (int u = 0; u < n; ++u) c[u + 1] = c[u] + std::max(1, (rg[u + 1] - rg[u] + CS - 1) / CS);
   }
-}
-
-// First-maximum argmax over a 256-thread workgroup: (v, j) with v > 0, or (0, INT32_MAX).
-__device__ __forceinline__ void block_argmax(double &v, int &j, double *sv, int *sj) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double v2 = __shfl_xor(v, off, 64);
-    const int j2 = __shfl_xor(j, off, 64);
-    if (v2 > v || (v2 == v && j2 < j)) {
-      v = v2;
-      j = j2;
-    }
-  }
-  const int w = threadIdx.x >> 6;
-  __syncthreads();  // the previous call's readers are done
-  if ((threadIdx.x & 63) == 0) {
-    sv[w] = v;
-    sj[w] = j;
-  }
-  __syncthreads();
-  v = sv[0];
-  j = sj[0];
-#pragma unroll
-  for (int q = 1; q < 4; ++q)
-    if (sv[q] > v || (sv[q] == v && sj[q] < j)) {
-      v = sv[q];
-      j = sj[q];
-    }
 }
 
 // ---------------------------------------------------------------- stage 6: per-utterance crude
@@ -742,50 +656,26 @@ __global__ void __launch_bounds__(256) ta_pick_utt(int64_t B, const int *__restr
   if (b >= B || u >= nutt[b]) return;
   const int tid = threadIdx.x;
   const int c0 = cs[b * (MAXU + 1) + u], m = cs[b * (MAXU + 1) + u + 1] - c0;
-  const float *P = part + (b * nslot + c0) * (int64_t)(NGRP * LG);
+  const float *P = part + (b * nslot + c0) * (int64_t)PART_LD;
   const int d0 = ucrude[b * MAXU + u];
-  double tot[3], left[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) tot[q] = 0.0;
-  for (int i = 0; i < m; ++i)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int l = tid + 256 * q;
-      if (l < NLAG) tot[q] += P[i * (NGRP * LG) + l];
-    }
-  // the thread's first peak (lags ascending) of an array given per q
-  auto local_peak = [&](const double *a, double &v, int &j) {
-    v = 0.0;
-    j = INT32_MAX;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int l = tid + 256 * q;
-      if (l < NLAG && a[q] > v) {
-        v = a[q];
-        j = l;
-      }
-    }
-  };
+  double tot[3] = {0.0, 0.0, 0.0}, left[3] = {0.0, 0.0, 0.0};
+  add_pieces(P, m, tid, tot);
   double vW;
   int iW;
-  local_peak(tot, vW, iW);
+  first_peak(tot, tid, vW, iW);
   block_argmax(vW, iW, sv, sj);
   double bestT = -1.0, bvL = 0.0, bvR = 0.0;
   int bs = -1, biL = INT32_MAX, biR = INT32_MAX;
   for (int s = 1; s + 1 < m && m >= 4; ++s) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int l = tid + 256 * q;
-      if (l < NLAG) left[q] += P[(s - 1) * (NGRP * LG) + l];
-    }
+    add_pieces(P + (s - 1) * PART_LD, 1, tid, left);  // the running sum of pieces < s
     if (s < 2) continue;
     double right[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) right[q] = tot[q] - left[q];
     double vL, vR;
     int iL, iR;
-    local_peak(left, vL, iL);
-    local_peak(right, vR, iR);
+    first_peak(left, tid, vL, iL);
+    first_peak(right, tid, vR, iR);
     block_argmax(vL, iL, sv, sj);
     block_argmax(vR, iR, sv, sj);
     if (vL + vR > bestT) {  // uniform: every thread holds the reduced values
@@ -808,29 +698,34 @@ __global__ void __launch_bounds__(256) ta_pick_utt(int64_t B, const int *__restr
   }
 }
 
-// One thread per row: the segments in order (equal neighbours merged), the row's delay (its
-// longest segment's, the first of equals).
+// One thread per row: the utterances' segments in order (equal neighbours merged, at most MAXSEG:
+// later ones merge into the last), the row's delay (its longest segment's, the first of equals).
+// An utterance's record of REC ints is {segments n <= REC / 2, the later segments' offsets from
+// the region's start, REC / 2 delays}: REC = 4 (ta_pick_utt, an offset in samples; at most
+// 2 MAXU = MAXSEG segments per row, so the cap is never reached) or USEG_P (ta_pick_p862, offsets
+// in pieces).
+template <int REC>
 __global__ void __launch_bounds__(64) ta_segments(int64_t B, int64_t L, const int32_t *__restrict__ lengths,
                                                   const int *__restrict__ nutt, const int *__restrict__ reg,
                                                   const int *__restrict__ useg, int *__restrict__ nseg,
                                                   int *__restrict__ seg_start, int *__restrict__ seg_delay,
                                                   int *__restrict__ delay) {
+  constexpr int UNIT = REC == 4 ? 1 : CS;  // samples per unit of offset
   const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   const int U = nutt[b];
   const int *rg = reg + b * (MAXU + 1);
   int *st = seg_start + b * (MAXSEG + 1), *dl = seg_delay + b * MAXSEG;
   int n = 0;
-  auto add = [&](int start, int d) {
-    if (n > 0 && dl[n - 1] == d) return;
-    st[n] = start;
-    dl[n] = d;
-    ++n;
-  };
   for (int u = 0; u < U; ++u) {
-    const int *o = useg + (b * MAXU + u) * 4;
-    add(rg[u], o[2]);
-    if (o[0] == 2) add(rg[u] + o[1], o[3]);
+    const int *o = useg + (b * MAXU + u) * REC;
+    for (int k = 0; k < o[0]; ++k) {
+      const int d = o[REC / 2 + k];
+      if ((n > 0 && dl[n - 1] == d) || n == MAXSEG) continue;
+      st[n] = rg[u] + (k ? o[k] : 0) * UNIT;
+      dl[n] = d;
+      ++n;
+    }
   }
   st[n] = (int)row_length(lengths, b, L);
   int best = -1, d = 0;
@@ -860,20 +755,11 @@ __global__ void __launch_bounds__(256) ta_shift_seg(const float *__restrict__ de
   if (n >= L) return;
   const int64_t Lr = row_length(lengths, b, L);
   const float *y = deg + b * ld;
-  int k = 0;
-  while (k + 1 < n_s && st[k + 1] <= n) ++k;
-  float v[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    while (k + 1 < n_s && st[k + 1] <= n + i) ++k;
-    const int64_t m = n + i + dl[k];
-    v[i] = (n + i < Lr && m >= 0 && m < Lr) ? y[m] : 0.f;
-  }
-  if (n + 4 <= L) {
-    *reinterpret_cast<float4 *>(out + b * ld_out + n) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    for (int i = 0; i < 4 && n + i < L; ++i) out[b * ld_out + n + i] = v[i];
-  }
+  int k = 0;  // the segment holding the output asked for (outputs ascending)
+  store4(out + b * ld_out, n, L, [&](int64_t p) {
+    while (k + 1 < n_s && st[k + 1] <= p) ++k;
+    return p < Lr ? fetch(y, p + dl[k], Lr) : 0.f;
+  });
 }
 
 // ---------------------------------------------------------------- P.862 mode stages 10-12
@@ -890,7 +776,7 @@ __global__ void __launch_bounds__(256) ta_piece_peaks(int64_t nslot_total, const
   const int64_t slot = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (slot >= nslot_total) return;  // wave-uniform
   const int lane = threadIdx.x & 63;
-  const float *P = part + slot * (int64_t)(NGRP * LG);
+  const float *P = part + slot * (int64_t)PART_LD;
   unsigned long long key = 0;
   for (int l = lane; l < NLAG; l += 64) {
     const float v = P[l];
@@ -922,7 +808,7 @@ __global__ void __launch_bounds__(256) ta_pick_p862(int64_t B, const int *__rest
                                                     const double *__restrict__ pwg, int *__restrict__ useg) {
   __shared__ double sv[4];
   __shared__ int sj[4];
-  __shared__ double H[NGRP * LG + 2 * HIST_T];  // lag l at H[HIST_T + l]; zero margins
+  __shared__ double H[PART_LD + 2 * HIST_T];  // lag l at H[HIST_T + l]; zero margins
   __shared__ double pw[PCACHE];                 // a piece's vote, 0 if it does not vote
   __shared__ int pg[PCACHE];                    // its lag index, -1 if it does not vote
   const int u = blockIdx.y;  // rows fastest in the dispatch order: a row's active workgroups spread over the XCDs
@@ -959,7 +845,7 @@ __global__ void __launch_bounds__(256) ta_pick_p862(int64_t B, const int *__rest
       pg[i] = ok ? lg[i] : -1;
       pw[i] = ok ? vw[i] : 0.0;
     }
-  for (int l = tid; l < NGRP * LG + 2 * HIST_T; l += 256)
+  for (int l = tid; l < PART_LD + 2 * HIST_T; l += 256)
     if (l < HIST_T || l >= HIST_T + NLAG) H[l] = 0.0;  // the margins, once: evaluations write every lag
   // (delay, confidence, votes) of pieces [a, e): every thread the same values
   auto eval = [&](int a, int e, int &D, double &conf, int &nv) {
@@ -1062,40 +948,6 @@ __global__ void __launch_bounds__(256) ta_pick_p862(int64_t B, const int *__rest
   }
 }
 
-// One thread per row: the utterances' segments in order (equal neighbours merged, at most MAXSEG:
-// later ones merge into the last), the row's delay (its longest segment's, the first of equals).
-__global__ void __launch_bounds__(64) ta_segments_p862(int64_t B, int64_t L, const int32_t *__restrict__ lengths,
-                                                       const int *__restrict__ nutt, const int *__restrict__ reg,
-                                                       const int *__restrict__ useg, int *__restrict__ nseg,
-                                                       int *__restrict__ seg_start, int *__restrict__ seg_delay,
-                                                       int *__restrict__ delay) {
-  const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  const int U = nutt[b];
-  const int *rg = reg + b * (MAXU + 1);
-  int *st = seg_start + b * (MAXSEG + 1), *dl = seg_delay + b * MAXSEG;
-  int n = 0;
-  for (int u = 0; u < U; ++u) {
-    const int *o = useg + (b * MAXU + u) * USEG_P;
-    for (int k = 0; k < o[0]; ++k) {
-      const int d = o[4 + k];
-      if ((n > 0 && dl[n - 1] == d) || n == MAXSEG) continue;
-      st[n] = rg[u] + (k ? o[k] : 0) * CS;
-      dl[n] = d;
-      ++n;
-    }
-  }
-  st[n] = (int)row_length(lengths, b, L);
-  int best = -1, d = 0;
-  for (int k = 0; k < n; ++k)
-    if (st[k + 1] - st[k] > best) {
-      best = st[k + 1] - st[k];
-      d = dl[k];
-    }
-  if (nseg) nseg[b] = n;
-  if (delay) delay[b] = d;
-}
-
 // ---------------------------------------------------------------- bad intervals (steps 13-15)
 // P.862's realignment of bad intervals (section 10.7 as restated in oracle/align_oracle.py steps
 // 13-15) on the per-frame disturbances of the aligned row (fsem_pesq_distances_f32's frames).
@@ -1105,10 +957,10 @@ constexpr int BAD_MIN = 5;       // frames: shorter intervals are dropped
 constexpr int MAXBAD = 16;       // intervals per row (include/fsem.h FSEM_PESQ_MAX_BAD)
 constexpr int HOP = 256;         // samples per PESQ frame hop
 
-// One wave per row: the symmetric disturbances 64 frames at a time (a ballot of the bad frames),
-// the runs walked with bit scans in wave-uniform code as ta_utterances; then (lane 0) each
+// One wave per row: the runs of frames whose symmetric disturbance is bad (walk_runs), joined
+// across gaps < BAD_GAP frames, kept from BAD_MIN frames, at most MAXBAD; then (lane 0) each
 // interval's samples [256 f0, min(256 f1 + 256, L_row)), the delay of the segment holding its
-// first sample, and its 5120-sample pieces as slot descriptors for ta_fine_partial.
+// first sample, and its 5120-sample pieces as the fine stage's slot descriptors (UttTables).
 __global__ void __launch_bounds__(64) ta_bad_find(int64_t B, int64_t L, const int32_t *__restrict__ lengths,
                                                   const float *__restrict__ frames, int64_t Fcap,
                                                   const int *__restrict__ nseg, const int *__restrict__ seg_start,
@@ -1122,7 +974,7 @@ __global__ void __launch_bounds__(64) ta_bad_find(int64_t B, int64_t L, const in
   const int64_t Lr = row_length(lengths, b, L);
   const int F = std::min<int64_t>(pesq::frames_of(Lr), Fcap);
   const float *sym = frames + 2 * b * Fcap;
-  int n = 0, s0 = -1, e0 = -1, rs = -1;  // intervals, joined run [s0, e0), open raw run from rs
+  int n = 0, s0 = -1, e0 = -1;  // intervals, joined run [s0, e0)
   auto flush = [&]() {
     if (s0 >= 0 && e0 - s0 >= BAD_MIN && n < MAXBAD) {
       if (lane == 0) {
@@ -1132,7 +984,7 @@ __global__ void __launch_bounds__(64) ta_bad_find(int64_t B, int64_t L, const in
       ++n;
     }
   };
-  auto close_run = [&](int k) {  // the raw run [rs, k) ends
+  auto close_run = [&](int rs, int k) {  // the raw run [rs, k) ends
     if (s0 >= 0 && rs - e0 < BAD_GAP) {
       e0 = k;
     } else {
@@ -1140,27 +992,9 @@ __global__ void __launch_bounds__(64) ta_bad_find(int64_t B, int64_t L, const in
       s0 = rs;
       e0 = k;
     }
-    rs = -1;
   };
-  for (int k0 = 0; k0 < (F >= 20 ? F : 0); k0 += 64) {
-    const int k = k0 + lane;
-    const uint64_t m = __ballot(k < F && sym[k] > BAD_THR);
-    int pos = 0;
-    while (pos < 64) {
-      if (rs >= 0) {
-        const uint64_t z = ~m >> pos;
-        if (z == 0) break;
-        pos += __builtin_ctzll(z);
-        close_run(k0 + pos);
-      } else {
-        const uint64_t o = m >> pos;
-        if (o == 0) break;
-        pos += __builtin_ctzll(o);
-        rs = k0 + pos;
-      }
-    }
-  }
-  if (rs >= 0) close_run(F);
+  // (rows of fewer than 20 frames have no PESQ score: no intervals)
+  walk_runs(F >= 20 ? F : 0, lane, [&](int k) { return sym[k] > BAD_THR; }, close_run);
   flush();
   __syncthreads();
   if (lane == 0) {
@@ -1199,20 +1033,11 @@ __global__ void __launch_bounds__(256) ta_bad_pick(int64_t B, const int *__restr
   if (b >= B || i >= n_bad[b]) return;
   const int tid = threadIdx.x;
   const int c0 = cs_bad[b * (MAXBAD + 1) + i], m = cs_bad[b * (MAXBAD + 1) + i + 1] - c0;
-  const float *P = part + (b * nslot + c0) * (int64_t)(NGRP * LG);
-  double v = 0.0;
-  int j = INT32_MAX;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int l = tid + 256 * q;
-    if (l >= NLAG) continue;
-    double t = 0.0;
-    for (int s = 0; s < m; ++s) t += P[s * (NGRP * LG) + l];
-    if (t > v) {
-      v = t;
-      j = l;
-    }
-  }
+  const float *P = part + (b * nslot + c0) * (int64_t)PART_LD;
+  double t[3] = {0.0, 0.0, 0.0}, v;
+  int j;
+  add_pieces(P, m, tid, t);
+  first_peak(t, tid, v, j);
   block_argmax(v, j, sv, sj);
   if (tid == 0 && j != INT32_MAX) {
     int *o = bad + (b * MAXBAD + i) * 3;
@@ -1242,26 +1067,14 @@ __global__ void __launch_bounds__(256) ta_bad_shift(const float *__restrict__ de
   const int64_t n = 4 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
   if (n >= L) return;
   const float *y = deg + b * ld;
-  float *r = out + b * ld_out;
   const float *a = aligned + b * ld_out;
-  float v[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
+  store4(out + b * ld_out, n, L, [&](int64_t p) {
     int k = -1;
     for (int q = 0; q < nb; ++q)
-      if (n + t >= lo[q] && n + t < hi[q]) k = q;
-    if (k < 0) {
-      v[t] = (n + t < L) ? a[n + t] : 0.f;
-    } else {
-      const int64_t m = n + t + dl[k];
-      v[t] = (m >= 0 && m < Lr) ? y[m] : 0.f;
-    }
-  }
-  if (n + 4 <= L) {
-    *reinterpret_cast<float4 *>(r + n) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    for (int t = 0; t < 4 && n + t < L; ++t) r[n + t] = v[t];
-  }
+      if (p >= lo[q] && p < hi[q]) k = q;
+    if (k < 0) return p < L ? a[p] : 0.f;
+    return fetch(y, p + dl[k], Lr);
+  });
 }
 
 // One wave per row: each interval takes the second row's frames when their symmetric sum is
@@ -1347,7 +1160,7 @@ inline Ws layout(Arena &a, int64_t B, int64_t L) {
   w.E = a.take<float>(2 * B * env_cap(L));
   w.crude = a.take<int>(B);
   w.delay = a.take<int>(B);
-  w.part = a.take<float>(B * nchunks(L) * NGRP * LG);
+  w.part = a.take<float>(B * nchunks(L) * PART_LD);
   return w;
 }
 
@@ -1365,7 +1178,7 @@ struct UttWs {
 inline UttWs utt_layout(Arena &a, int64_t B, int64_t L, bool p862) {
   UttWs w{};
   w.E = a.take<float>(2 * B * env_cap(L));
-  w.part = a.take<float>(B * nslots(L) * NGRP * LG);
+  w.part = a.take<float>(B * nslots(L) * PART_LD);
   w.crude = a.take<int>(B);
   w.delay = a.take<int>(B);
   w.nutt = a.take<int>(B);
@@ -1398,12 +1211,12 @@ inline BadWs bad_layout(Arena &a, int64_t B, int64_t L) {
   w.desc = a.take<int4>(B * bad_nslots(L));
   w.ndesc = a.take<int>(B);
   w.cs = a.take<int>(B * (MAXBAD + 1));
-  w.part = a.take<float>(B * bad_nslots(L) * NGRP * LG);
+  w.part = a.take<float>(B * bad_nslots(L) * PART_LD);
   return w;
 }
 
-// What the row mode and the segmented modes share.  The argument checks (`pieces`: fine-stage
-// pieces per row, whose batch total is a 32-bit grid size) ...
+// What the entries share.  The argument checks of the rows and of the output that ld_out
+// describes (`pieces`: fine-stage pieces per row, whose batch total is a 32-bit grid size) ...
 inline bool args_ok(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld, int32_t max_delay,
                     const float *deg_aligned, int64_t ld_out, int64_t pieces) {
   return ref && deg && batch > 0 && length > 0 && ld >= length && length <= kMaxLength && max_delay >= 0 &&
@@ -1447,14 +1260,14 @@ extern "C" int fsem_time_align_f32(const float *ref, const float *deg, int64_t b
   const int64_t nch = align::nchunks(length);
   const int rc = align::launch_crude(ref, deg, batch, length, ld, lengths, max_delay, w.E, w.crude, st);
   if (rc != FSEM_OK) return rc;
-  align::launch_fine((unsigned)(batch * nch), st, ref, deg, batch, length, ld, lengths, w.crude, (int)nch, w.part,
-                     align::UttTables{});
+  align::ta_fine_fft<<<(unsigned)(batch * nch), 256, 0, st>>>(ref, deg, batch, length, ld, lengths, w.crude, (int)nch,
+                                                              w.part, align::UttTables{});
   FSEM_CHECK_LAUNCH();
   align::ta_fine_pick<<<grid_xy(batch), 256, 0, st>>>(batch, w.crude, (int)nch, w.part, dl);
   FSEM_CHECK_LAUNCH();
   if (deg_aligned) {
-    align::ta_shift<<<grid_yz((unsigned)((length + 1023) / 1024), batch), 256, 0, st>>>(deg, batch, length, ld, lengths,
-                                                                                       dl, deg_aligned, ld_out);
+    align::ta_shift<<<align::shift_grid(length, batch), 256, 0, st>>>(deg, batch, length, ld, lengths, dl,
+                                                                      deg_aligned, ld_out);
     FSEM_CHECK_LAUNCH();
   }
   return FSEM_OK;
@@ -1500,27 +1313,27 @@ static int time_align_segmented(bool p862, const float *ref, const float *deg, i
   align::ta_crude_utt<<<per_utt, 256, 0, st>>>(batch, length, lengths, w.E, nfr_cap, align::lag_frames(max_delay),
                                                w.crude, w.nutt, w.utt, w.ucrude);
   FSEM_CHECK_LAUNCH();
-  align::launch_fine((unsigned)(batch * nsl), st, ref, deg, batch, length, ld, lengths, w.crude, (int)nsl, w.part,
-                     align::UttTables{w.nutt, w.reg, w.cs, w.ucrude});
+  align::ta_fine_fft<<<(unsigned)(batch * nsl), 256, 0, st>>>(ref, deg, batch, length, ld, lengths, w.crude, (int)nsl,
+                                                              w.part, align::UttTables{w.nutt, w.reg, w.cs, w.ucrude});
   FSEM_CHECK_LAUNCH();
   if (p862) {
     align::ta_piece_peaks<<<(unsigned)((batch * nsl + 3) / 4), 256, 0, st>>>(batch * nsl, w.part, w.pv, w.pl, w.pw);
     FSEM_CHECK_LAUNCH();
     align::ta_pick_p862<<<per_utt, 256, 0, st>>>(batch, w.nutt, w.cs, w.ucrude, (int)nsl, w.pv, w.pl, w.pw, w.useg_p);
     FSEM_CHECK_LAUNCH();
-    align::ta_segments_p862<<<(unsigned)((batch + 63) / 64), 64, 0, st>>>(batch, length, lengths, w.nutt, w.reg,
-                                                                          w.useg_p, ns, ss, sd, dl);
+    align::ta_segments<align::USEG_P><<<(unsigned)((batch + 63) / 64), 64, 0, st>>>(
+        batch, length, lengths, w.nutt, w.reg, w.useg_p, ns, ss, sd, dl);
     FSEM_CHECK_LAUNCH();
   } else {
     align::ta_pick_utt<<<per_utt, 256, 0, st>>>(batch, w.nutt, w.cs, w.ucrude, (int)nsl, w.part, w.useg);
     FSEM_CHECK_LAUNCH();
-    align::ta_segments<<<(unsigned)((batch + 63) / 64), 64, 0, st>>>(batch, length, lengths, w.nutt, w.reg, w.useg,
-                                                                   ns, ss, sd, dl);
+    align::ta_segments<4><<<(unsigned)((batch + 63) / 64), 64, 0, st>>>(batch, length, lengths, w.nutt, w.reg, w.useg,
+                                                                        ns, ss, sd, dl);
     FSEM_CHECK_LAUNCH();
   }
   if (deg_aligned) {
-    align::ta_shift_seg<<<grid_yz((unsigned)((length + 1023) / 1024), batch), 256, 0, st>>>(
-        deg, batch, length, ld, lengths, ns, ss, sd, deg_aligned, ld_out);
+    align::ta_shift_seg<<<align::shift_grid(length, batch), 256, 0, st>>>(deg, batch, length, ld, lengths, ns, ss, sd,
+                                                                          deg_aligned, ld_out);
     FSEM_CHECK_LAUNCH();
   }
   return FSEM_OK;
@@ -1555,12 +1368,11 @@ extern "C" int fsem_pesq_bad_intervals_f32(const float *ref, const float *deg, c
                                            const int32_t *seg_delay, int32_t *n_bad, int32_t *bad,
                                            float *deg_second, int64_t ld_out, void *ws, size_t ws_bytes,
                                            void *stream) {
-  if (!ref || !deg || !deg_aligned || !frames || !n_seg || !seg_start || !seg_delay || !n_bad || !bad ||
-      !deg_second || batch <= 0 || length <= 0 || ld < length || length > kMaxLength || ld_out < length ||
-      ld_out % 4 != 0 || ld % 4 != 0)
-    return FSEM_EINVAL;
   const int64_t nsl = align::bad_nslots(length);
-  if (batch * nsl > INT32_MAX) return FSEM_EINVAL;
+  // (no crude search: max_delay 0; the second row is the output that ld_out describes)
+  if (!align::args_ok(ref, deg, batch, length, ld, 0, deg_second, ld_out, nsl) || !deg_second || !deg_aligned ||
+      !frames || !n_seg || !seg_start || !seg_delay || !n_bad || !bad)
+    return FSEM_EINVAL;
   Arena a(ws);
   const align::BadWs w = align::bad_layout(a, batch, length);
   if (!a.fits(ws_bytes)) return FSEM_EWORKSPACE;
@@ -1572,13 +1384,13 @@ extern "C" int fsem_pesq_bad_intervals_f32(const float *ref, const float *deg, c
   align::UttTables ut{};
   ut.desc = w.desc;
   ut.ndesc = w.ndesc;
-  align::launch_fine((unsigned)(batch * nsl), st, ref, deg, batch, length, ld, lengths, nullptr, (int)nsl, w.part,
-                     ut);
+  align::ta_fine_fft<<<(unsigned)(batch * nsl), 256, 0, st>>>(ref, deg, batch, length, ld, lengths, nullptr, (int)nsl,
+                                                              w.part, ut);
   FSEM_CHECK_LAUNCH();
   align::ta_bad_pick<<<grid_xz(batch, align::MAXBAD), 256, 0, st>>>(batch, n_bad, w.cs, (int)nsl, w.part, bad);
   FSEM_CHECK_LAUNCH();
-  align::ta_bad_shift<<<grid_yz((unsigned)((length + 1023) / 1024), batch), 256, 0, st>>>(
-      deg, deg_aligned, batch, length, ld, lengths, n_bad, bad, deg_second, ld_out);
+  align::ta_bad_shift<<<align::shift_grid(length, batch), 256, 0, st>>>(deg, deg_aligned, batch, length, ld, lengths,
+                                                                        n_bad, bad, deg_second, ld_out);
   FSEM_CHECK_LAUNCH();
   return FSEM_OK;
 }

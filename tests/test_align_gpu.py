@@ -74,6 +74,28 @@ def test_engine_unbounded_max_delay(dev):
     np.testing.assert_array_equal(ds.cpu().numpy(), D)
 
 
+def test_engine_crude_on_both_sides_of_its_lds_capacity(dev):
+    """Rows of 6146 and 6144 envelope frames in one batch: ta_crude keeps up to 6144 frames per
+    signal in LDS and reads longer rows from global memory.  Both rows recover their known delay
+    and equal the package's CPU path and the oracle, aligned rows bitwise."""
+    from fast_speech_enhancement_metrics_amd.alignment import time_align
+    from fast_speech_enhancement_metrics_amd.synthetic import speech_like_pairs
+    L = 64 * 6146
+    c, n, _ = speech_like_pairs(2, L, 16000, seed=37)
+    D = np.array([2345, -610])
+    c, deg = c.numpy(), np.stack([A.shift(n[b].numpy(), -int(D[b])) for b in range(2)])
+    lens = np.array([L, L - 128], dtype=np.int32)
+    al, ds = time_align(torch.from_numpy(c).to(dev), torch.from_numpy(deg).to(dev),
+                        lengths=torch.from_numpy(lens).to(dev))
+    cal, cds = time_align(torch.from_numpy(c), torch.from_numpy(deg), lengths=torch.from_numpy(lens))
+    oal, ods = A.align(c, deg, lengths=lens)
+    np.testing.assert_array_equal(ds.cpu().numpy(), D)
+    np.testing.assert_array_equal(ds.cpu().numpy(), cds.numpy())
+    np.testing.assert_array_equal(ds.cpu().numpy(), ods)
+    np.testing.assert_array_equal(al.cpu().numpy(), cal.numpy())
+    np.testing.assert_array_equal(al.cpu().numpy(), oal)
+
+
 def test_pesq_time_align_on_gpu(dev):
     from fast_speech_enhancement_metrics_amd import PESQ
     c, deg, D = _delayed(12, 48000, 33, 3000)

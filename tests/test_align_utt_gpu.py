@@ -57,6 +57,31 @@ def test_engine_ragged_empty_and_bounded(dev):
     _check(res, want, c.shape[0])
 
 
+@pytest.mark.parametrize("mode", ["utterance", "p862"])
+def test_engine_long_utterance_on_both_sides_of_its_lds_capacity(dev, mode):
+    """One continuous utterance per row, 4200 and 4000 envelope frames long (seeds 21 and 22: the
+    envelope cuts neither): ta_crude_utt stages search windows of up to 4096 frames in LDS and
+    reads longer ones from global memory.  Both rows recover their known delay; delays, segments
+    and aligned rows equal the package's CPU path."""
+    L = 64 * 4200
+    D = [700, -450]
+    rows = [AC.continuous_pair(21 + b, L, [(0, L, D[b])]) for b in range(2)]
+    c, d = np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
+    lens = [L, 64 * 4000]
+    g = [t.cpu().numpy() for t in time_align_segments(torch.from_numpy(c).to(dev), torch.from_numpy(d).to(dev),
+                                                      lengths=lens, mode=mode)]
+    h = [t.numpy() for t in time_align_segments(torch.from_numpy(c), torch.from_numpy(d), lengths=lens, mode=mode)]
+    np.testing.assert_array_equal(h[1], D)
+    np.testing.assert_array_equal(h[2], [1, 1])
+    for b in range(2):
+        np.testing.assert_array_equal(h[3][b, :2], [0, lens[b]])
+    for i in (0, 1, 2):  # aligned rows, delays, n_seg
+        np.testing.assert_array_equal(g[i], h[i])
+    for b in range(2):
+        np.testing.assert_array_equal(g[3][b, :2], h[3][b, :2])
+        np.testing.assert_array_equal(g[4][b, :1], h[4][b, :1])
+
+
 def test_pesq_utterance_mode(dev):
     from fast_speech_enhancement_metrics_amd import PESQ
     c, d = AC.batch()

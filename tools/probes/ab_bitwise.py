@@ -9,6 +9,8 @@ With ``--metrics composite,spectral,bsssdr,bsseval``: every score tensor of thos
 SpectralMeasures' frame values) into one .npz, the package imported from ``--root`` (a built tree;
 default: this one), which locates its own libraries.  Small shapes on each side of the kernels'
 chunk, group, window and piece sizes, and with ``--large`` the shapes the rate probes time.
+``align``: the time alignment's outputs in its three modes, the bad intervals' realignment and the
+aligned PESQ scores (align_inputs).
 
     python tools/probes/ab_bitwise.py a.npz --metrics composite,spectral --root other/tree
     python tools/probes/ab_bitwise.py b.npz --metrics composite,spectral --compare a.npz
@@ -24,7 +26,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("out")
 ap.add_argument("--compare")
 ap.add_argument("--batch", type=int, default=1024)
-ap.add_argument("--metrics", default="", help="comma-separated: composite, spectral, bsssdr, bsseval")
+ap.add_argument("--metrics", default="", help="comma-separated: composite, spectral, bsssdr, bsseval, align")
 ap.add_argument("--root", default=os.path.join(os.path.dirname(__file__), "..", ".."),
                 help="the tree to import the package (and the tests' seeded cases) from")
 ap.add_argument("--large", action="store_true", help="the rate probes' shapes instead of the small ones")
@@ -108,6 +110,62 @@ def run_bsseval(out):
                 out[f"bsseval/{S}x{E}x{L}/{key}"] = host(t)
 
 
+def align_inputs():
+    """(name, clean, degraded, lengths) for the time alignment: the tests' designed cases (utterances
+    with known delays, three delays inside one utterance, bad intervals), a ragged batch on each
+    side of the envelope frame (64), the fine stage's block (1280) and piece (5120), and rows on
+    each side of the crude stages' LDS capacities (6144 envelope frames per row, 4096 per
+    utterance window)."""
+    from tests import align_cases as AC
+
+    def delayed(x, D):  # y[n] = x[n - D] inside the row, else 0
+        y = np.roll(x, D)
+        if D > 0:
+            y[:D] = 0
+        elif D < 0:
+            y[D:] = 0
+        return y
+
+    def pairs(B, L, seed, D):
+        c, n, _ = speech_like_pairs(B, L, 16000, seed=seed)
+        return c.numpy(), np.stack([delayed(n[b].numpy(), int(D[b])) for b in range(B)])
+
+    yield ("cases",) + AC.batch() + (None,)
+    yield ("cases11",) + AC.batch(seed0=11) + ([AC.L_UTT, 50000, 0, 700],)
+    rows = [AC.continuous_pair(3 + k, AC.L_CONT, AC.CONT_PIECES) for k in range(4)]
+    yield "continuous", np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows]), None
+    yield ("bad",) + AC.bad_batch() + (None,)
+    yield ("ragged",) + pairs(8, 40001, 32, [0, 5, -7, 300, -200, 1000, -1500, 2500]) + (
+        [0, 63, 64, 1279, 1281, 5119, 5121, 40001],)
+    L = 64 * 6146
+    yield ("long_rows",) + pairs(2, L, 37, [2345, -610]) + ([L, L - 128],)
+    L = 64 * 4200
+    rows = [AC.continuous_pair(21 + b, L, [(0, L, D)]) for b, D in enumerate([700, -450])]
+    yield "long_utterances", np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows]), [L, 64 * 4000]
+
+
+def run_align(out):
+    from fast_speech_enhancement_metrics_amd import PESQ
+    from fast_speech_enhancement_metrics_amd.alignment import realign_bad_intervals, time_align, time_align_segments
+    for name, c, d, lens in align_inputs():
+        ct, dt = torch.from_numpy(c).cuda(), torch.from_numpy(d).cuda()
+        lens = None if lens is None else torch.tensor(lens, dtype=torch.int32, device="cuda")
+        for key, t in zip(("aligned", "delay"), time_align(ct, dt, lengths=lens)):
+            out[f"align/{name}/row/{key}"] = host(t)
+        for mode in ("utterance", "p862"):
+            seg = time_align_segments(ct, dt, lengths=lens, mode=mode)
+            for key, t in zip(("aligned", "delay", "n_seg", "seg_start", "seg_delay"), seg):
+                out[f"align/{name}/{mode}/{key}"] = host(t)
+        m = PESQ(16000, use_gpu=True, time_align="p862")
+        fr1 = m.frame_disturbances(ct, seg[0], lengths=lens)[2]
+        bad = realign_bad_intervals(ct, dt, seg[0], fr1, *seg[2:], lengths=lens)
+        for key, t in zip(("n_bad", "bad", "second"), bad):
+            out[f"align/{name}/bad/{key}"] = host(t)
+        for mode in ("row", "utterance", "p862"):
+            s = PESQ(16000, use_gpu=True, time_align=mode).scores(ct, dt, lengths=lens)
+            out[f"align/{name}/pesq/{mode}"] = host(s)
+
+
 if not a.metrics:
     from fast_speech_enhancement_metrics_amd import PESQ_STOI
     c, n, _ = speech_like_pairs(a.batch, 160000, device="cuda")
@@ -123,7 +181,8 @@ if not a.metrics:
 
 res = {}
 for name in a.metrics.split(","):
-    {"composite": run_composite, "spectral": run_spectral, "bsssdr": run_bsssdr, "bsseval": run_bsseval}[name](res)
+    {"composite": run_composite, "spectral": run_spectral, "bsssdr": run_bsssdr, "bsseval": run_bsseval,
+     "align": run_align}[name](res)
 torch.cuda.synchronize()
 np.savez(a.out, **res)
 if a.compare:
