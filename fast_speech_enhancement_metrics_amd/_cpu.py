@@ -818,6 +818,24 @@ def lsd(clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
     return v.to(torch.float32)
 
 
+def lsd64(clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
+    """[B, n] 16 kHz rows -> lsd [B] float64, differentiable with respect to ``noisy`` under autograd:
+    ``lsd``'s operations with the magnitudes as roots of re^2 + im^2.  Both roots (the estimate's
+    magnitude, the frame's value) take the subgradient 0 at 0 (``_Sqrt0``), as the engine's backward: a
+    silent estimate frame, or a silent estimate, gets an exactly zero gradient."""
+    s = clean.to(torch.float64)
+    h = noisy.to(torch.float64)
+    B = s.shape[0]
+    a = (s * h).sum(1, keepdim=True) / (h.square().sum(1, keepdim=True) + 1e-8)
+    x = torch.nn.functional.pad(torch.cat([s, h * a]), (256, 256))
+    w = torch.hann_window(512, dtype=torch.float64, device=x.device)
+    z = torch.view_as_real(torch.stft(x, n_fft=512, hop_length=256, window=w, center=False, return_complex=True))
+    S2 = z[:B].square().sum(-1)
+    H = _Sqrt0.apply(z[B:].square().sum(-1))
+    t = torch.log(S2 / (H + 1e-8).square() + 1e-8)
+    return _Sqrt0.apply(t.square().mean(1)).mean(1)
+
+
 # ----------------------------------------------------------------------------- BSS-eval SDR
 # The reference's SDR (SDR.py:7-97; engine: csrc/bsssdr.hip, definition: include/fsem_bsssdr.h):
 # float32 normalisation as the reference's, then float64: linear correlations for 512 lags and a

@@ -110,6 +110,12 @@ SIGNATURES = {
     "fsem_pesq_state_floats": (_c_i64, [_c_i64, _c_i64]),
     "fsem_pesq_state_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp]),
     "fsem_pesq_grad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "fsem_lsd_grad_state_floats": (_c_i64, [_c_i64, _c_i64]),
+    "fsem_lsd_grad_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "fsem_lsd_grad_rate_state_floats": (_c_i64, [_c_i64, _c_i64, _c_i32]),
+    "fsem_lsd_grad_rate_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _c_i64,
+                                               _vp]),
+    "fsem_resample_rows_grad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_i32, _c_i32, _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

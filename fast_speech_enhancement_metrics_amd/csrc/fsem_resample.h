@@ -62,4 +62,47 @@ __device__ __forceinline__ float resample_at(const float *__restrict__ x, int64_
   return acc;
 }
 
+// The resampler's transpose (fsem_resample_rows_grad_f32; on a double gradient: fsem_lsd_grad_rate_f32): grad_in[r, i] = sum_o K[o mod nw][i - first(o)] g_out[r, o] over the row's output
+// samples o = m nw + j < ceil(n nw / orig) whose taps reach input sample i (first(o) = m orig - width),
+// m then j ascending; 0 from the row's length n on.  One thread per input sample, the forward's
+// float32 taps, the sum in double and rounded once.  Any rate pair (a large table's coefficients are
+// evaluated where they are used, by the forward's formula).
+constexpr int RS_GRAD_T = 256;
+template <class G>
+__global__ void __launch_bounds__(RS_GRAD_T) resample_rows_grad(const G *__restrict__ g_out, int64_t n_in, int64_t ld_out,
+                                                          const int32_t *__restrict__ lens, float *__restrict__ grad_in,
+                                                          int64_t ld_in, int64_t r0, ResampleKernel rk) {
+  __shared__ float ks[FSEM_RS_MAX_COEF];
+  const int tid = threadIdx.x;
+  const int64_t r = r0 + blockIdx.y;
+  const int orig = rk.orig, nw = rk.nw, taps = rk.taps, width = rk.width;
+  if (!rk.big)
+    for (int i = tid; i < nw * taps; i += RS_GRAD_T) ks[i] = rk.k[i];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * RS_GRAD_T + tid;
+  if (i >= n_in) return;
+  int64_t n = n_in;
+  if (lens) {
+    const int64_t v = lens[r];
+    n = v < 0 ? 0 : (v > n_in ? n_in : v);
+  }
+  double acc = 0.0;
+  if (i < n) {
+    const int64_t n_out = (n * nw + orig - 1) / orig;
+    const G *__restrict__ g = g_out + r * ld_out;
+    const int64_t num = i + width - taps + 1;
+    const int64_t m_lo = num <= 0 ? 0 : (num + orig - 1) / orig;
+    const int64_t m_hi = (i + width) / orig;
+    for (int64_t m = m_lo; m <= m_hi; ++m) {
+      const int t = (int)(i - (m * orig - width));  // 0 <= t < taps
+      for (int j = 0; j < nw; ++j) {
+        const int64_t o = m * nw + j;
+        if (o < n_out)
+          acc = fma((double)(rk.big ? sinc_coef(j, t, orig, nw, width) : ks[j * taps + t]), (double)g[o], acc);
+      }
+    }
+  }
+  grad_in[r * ld_in + i] = (float)acc;
+}
+
 }  // namespace fsem

@@ -384,6 +384,26 @@ int launch_resample_tiled(const float *in, int64_t rows, int64_t n_in, int64_t l
 
 }  // namespace fsem
 
+extern "C" int fsem_resample_rows_grad_f32(const float *g_out, int64_t rows, int64_t n_in, int64_t ld_out,
+                                           const int32_t *lengths, float *grad_in, int64_t ld_in, int32_t orig_freq,
+                                           int32_t new_freq, void *stream) {
+  if (!g_out || !grad_in || rows < 0 || n_in < 0 || ld_in < n_in || n_in > fsem::kMaxLength) return FSEM_EINVAL;
+  if (orig_freq == new_freq) return FSEM_ERATE;  // nothing was resampled: the gradient is the caller's own
+  fsem::ResampleKernel rk;
+  const int rc = fsem::make_resample_kernel(orig_freq, new_freq, &rk);
+  if (rc != FSEM_OK) return rc;
+  const int64_t n_out = (rk.nw * n_in + rk.orig - 1) / rk.orig;
+  if (ld_out < n_out || n_out > fsem::kMaxLength) return FSEM_EINVAL;
+  if (rows == 0 || n_in == 0) return FSEM_OK;
+  for (int64_t r0 = 0; r0 < rows; r0 += fsem::kMaxGridY) {
+    hipLaunchKernelGGL(fsem::resample_rows_grad<float>,
+                       fsem::grid_slice((unsigned)((n_in + fsem::RS_GRAD_T - 1) / fsem::RS_GRAD_T), rows, r0),
+                       dim3(fsem::RS_GRAD_T), 0, (hipStream_t)stream, g_out, n_in, ld_out, lengths, grad_in, ld_in, r0, rk);
+    FSEM_CHECK_LAUNCH();
+  }
+  return FSEM_OK;
+}
+
 extern "C" int64_t fsem_resample_length(int64_t n_in, int32_t orig_freq, int32_t new_freq) {
   fsem::ResampleKernel rk;
   if (orig_freq == new_freq) return n_in;

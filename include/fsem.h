@@ -727,6 +727,84 @@ int fsem_pesq_grad_f32(const float *deg, int64_t batch, int64_t length, int64_t 
                        float *state, const float *g_mos, const float *g_sym, const float *g_asym,
                        float *grad, int64_t grad_ld, void *stream);
 
+/* ---------------------------------------------------------------- LSD with gradients
+ * The gradient of L = sum_b g_lsd[b] LSD_b with respect to the denoised rows at 16 kHz, LSD as
+ * fsem_lsd.h defines it (the forward entry fsem_lsd_f32 lives in libfsem_lsd.so; rows at another
+ * rate take fsem_lsd_grad_rate_f32, below).  (Joined at
+ * ABI 11 without a bump, as above.)  Per row, with s, h the first n samples, sh = sum s h, hh = sum h h,
+ * a = sh / (hh + 1e-8), y = a h, F = 1 + n / 256, S_k and H_k the 512-point spectra of w s and w y in
+ * frame f (bins 0 .. 256), q_k = |S_k|^2 / (|H_k| + 1e-8)^2, t_k = ln(q_k + 1e-8),
+ * v_f = sqrt(sum_k t_k^2 / 257), LSD = sum_f v_f / F:
+ *   d LSD / d|H_k| = t_k / (257 v_f F) * (-2 q_k / ((|H_k| + 1e-8)(q_k + 1e-8))),  G_k = that * H_k / |H_k|
+ *   xbar_t = Re sum_{k=0..256} G_k e^{+2 pi i k t / 512} (the adjoint of the one-sided transform: no factor 2
+ *            on the inner bins), times w_t, overlap-added over the frames: ybar
+ *   D = sum_t ybar_t h_t,  d LSD / d h_t = a ybar_t + D (s_t - 2 a h_t) / (hh + 1e-8),  grad = g_lsd[b] times that.
+ *  - Clean rows are constants: no gradient with respect to ref.
+ *  - |H_k| = 0 takes the subgradient 0: a silent estimate frame, or a silent estimate, gives exact zeros.
+ *    A frame with v_f = 0 contributes 0.  S = 0, a silent clean frame, gives 0 by the formula.
+ *  - A row with a non-finite sample in either operand among its lengths[b] samples (its score is NaN) gets
+ *    a gradient row of exact zeros; no other row is touched.
+ *  - With lengths, grad[b, lengths[b] .. length) is zero and row b's gradient is that of the unpadded row.
+ *    Columns of grad at or past `length` (grad_ld > length) are not written.
+ *  - Precision: everything is double up to the one rounding of the float32 store -- the sums, a, the window
+ *    products, both transforms, D -- and, unlike the forward's float32 log term, so are the root, the ratio
+ *    and the logarithm of each bin: the backward divides by v_f, and on near-identical rows t is of order
+ *    1e-6, where a float32 logarithm has lost most of its digits.
+ *  - No atomics; every sum has one order that depends on n alone; each overlap-added sample has at most
+ *    two addends.  A row's gradient is bitwise the same whatever the batch size, the row's position,
+ *    `length`, `ld`, `grad_ld`, the alignment (16-byte or 4-byte loads and stores) and the stream.
+ *  - Nothing of the forward call is kept: the entry recomputes sh, hh and a with the forward's own kernels
+ *    (bitwise the forward's a), so zero bytes of state outlive fsem_lsd_f32.
+ *
+ *   ref, deg : as fsem_lsd_f32 takes them ([batch, length] float32, row stride ld, readable up to
+ *              ceil4(length) floats per row)
+ *   g_lsd    : [batch] float32 device array
+ *   state    : [fsem_lsd_grad_state_floats(batch, length)] float32, owned by the caller, 256-byte aligned:
+ *              scratch (every part is written by the call that reads it; it may be reused across calls and
+ *              need not be kept): the twiddles, per row the scale, the chunk sums, one share of D per 16
+ *              frames and the first half-frame of every 16th frame, and ybar in double [ceil4(length)]:
+ *              about 8.6 bytes per sample.
+ *   grad     : [batch, length] float32, row b at grad + b grad_ld; every element of [b, 0 .. length) is
+ *              written.
+ * FSEM_EINVAL before any launch for null pointers (lengths may be NULL), batch < 1, length < 1, ld < length,
+ * grad_ld < length or length > 2^29 (fsem_lsd_grad_state_floats returns 0 for such batch and length).
+ */
+int64_t fsem_lsd_grad_state_floats(int64_t batch, int64_t length);  /* 0 for arguments the entry refuses */
+int fsem_lsd_grad_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                      const int32_t *lengths, const float *g_lsd, float *state,
+                      float *grad, int64_t grad_ld, void *stream);
+
+/* The same gradient for rows at another rate: ref, deg [batch, length] at sample_rate, grad [batch, length]
+ * the gradient with respect to deg at that rate, lengths at that rate.  The function differentiated is LSD of
+ * the rows resampled to 16 kHz (the taps of fsem_resample_rows_f32, each row as the row alone) WITHOUT the
+ * float32 rounding of the resampled rows: the entry resamples both rows itself with the sums in double, keeps
+ * them in double in the state, runs the kernels of fsem_lsd_grad_f32 on double rows, and pulls the gradient
+ * back through the transposed resampler in double; the float32 store of grad is the only rounding.  Rows
+ * resampled from 8 kHz have an upper half-spectrum 100 dB below a frame's peak, where the float32 rounding of
+ * a stored 16 kHz row (1e-7 of the peak) is a tenth of a bin: the gradient taken at such stored rows is 0.6 to
+ * 1.8 per cent away from this one on the tests' 8 kHz rows.  The scores stay those of fsem_lsd_f32 on the
+ * float32 rows the forward resampler stores.  Conventions, promises and refusals as above; in addition
+ * FSEM_ERATE for a rate without a resampling kernel and FSEM_EINVAL where the resampled length exceeds 2^29
+ * (fsem_lsd_grad_rate_state_floats returns 0 for both); sample_rate == 16000 is fsem_lsd_grad_f32 itself.
+ * The state adds both 16 kHz rows in double: about 24.6 bytes per 16 kHz sample. */
+int64_t fsem_lsd_grad_rate_state_floats(int64_t batch, int64_t length, int32_t sample_rate);
+int fsem_lsd_grad_rate_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                           const int32_t *lengths, int32_t sample_rate, const float *g_lsd, float *state,
+                           float *grad, int64_t grad_ld, void *stream);
+
+/* The transpose of fsem_resample_rows_f32 (and of fsem_resample_f32: lengths NULL), for any rate pair
+ * those take: g_out [rows, fsem_resample_length(n_in, ...)] (row stride ld_out) is the gradient with
+ * respect to the resampled rows, grad_in [rows, n_in] (row stride ld_in) the gradient with respect to the
+ * rows that were resampled, each row as the row alone: row r's first lengths[r] inputs collect the terms
+ * of its fsem_resample_length(lengths[r], ...) outputs, in ascending output order, with the forward's
+ * float32 taps, summed in double and rounded once; grad_in[r, lengths[r] .. n_in) is zero.  One thread
+ * per input sample, no atomics.  FSEM_EINVAL for null pointers (lengths may be NULL), rows < 0, n_in < 0,
+ * n_in > 2^29, ld_in < n_in or ld_out below the output length; FSEM_ERATE as the forward gives it (a
+ * filter above 8192 taps, orig_freq == new_freq); both before any launch. */
+int fsem_resample_rows_grad_f32(const float *g_out, int64_t rows, int64_t n_in, int64_t ld_out,
+                                const int32_t *lengths /* NULL: whole rows */, float *grad_in, int64_t ld_in,
+                                int32_t orig_freq, int32_t new_freq, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
