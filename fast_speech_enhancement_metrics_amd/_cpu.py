@@ -864,7 +864,18 @@ def bsssdr(clean: torch.Tensor, noisy: torch.Tensor, load_diag=None, filter_leng
     b = torch.fft.irfft(Sf.conj() * torch.fft.rfft(h, n=nfft), n=nfft)[:, :K].contiguous()
     if load_diag is not None:
         r[:, 0] += float(load_diag)
-    bad = ~finite | ~(r[:, 0] > 0)
+    x, bad = _toeplitz_solve(r, b, ~finite | ~(r[:, 0] > 0))
+    coh = (b * x).sum(1)
+    ratio = coh / (1.0 - coh).clamp(min=1e-8)
+    val = (10.0 * torch.log10(ratio.clamp(min=1e-8))).to(torch.float32)
+    return torch.where(bad | ~torch.isfinite(coh), nan, val)
+
+
+def _toeplitz_solve(r: torch.Tensor, b: torch.Tensor, bad: torch.Tensor):
+    """(x [B, K] with R x = b for R[i][j] = r[|i - j|], bad [B]) by the Levinson-Durbin recursion for a
+    general right-hand side; ``bad`` marks the rows given as bad and those whose prediction error is <= 0
+    at any order (their x is arbitrary but finite arithmetic)."""
+    B, K = r.shape
     r0 = torch.where(bad, torch.ones_like(r[:, 0]), r[:, 0])
     E = r0.clone()
     a = torch.zeros(B, K, dtype=torch.float64, device=r.device)  # the predictor [1, a1, ..., am]
@@ -882,10 +893,48 @@ def bsssdr(clean: torch.Tensor, noisy: torch.Tensor, load_diag=None, filter_leng
         E = torch.where(bad, torch.ones_like(E), E)  # (a row already NaN: keep the arithmetic finite)
         lam = (b[:, m] - q) / E
         x[:, :m + 1] = x[:, :m + 1] + lam[:, None] * a[:, :m + 1].flip(1)
-    coh = (b * x).sum(1)
+    return x, bad
+
+
+def bsssdr64(clean: torch.Tensor, noisy: torch.Tensor, load_diag=None) -> torch.Tensor:
+    """[1, n] 16 kHz rows -> SDR [1] float64 in dB, differentiable with respect to ``noisy`` under autograd
+    (include/fsem.h, "BSS-eval SDR with gradients"); NaN without a graph for a row ``bsssdr`` scores NaN.
+    The value is taken at the float32 quotients q = h / nh of ``bsssdr``; the estimate enters the graph as
+    h' = q + (d - q (q . d)) / nh with d = h - h.detach() (zero), i.e. with the Jacobian (I - q q^T) / nh of
+    the normalisation (d / nh where the norm sits at its clamp).  The system is solved without a graph (the
+    recursion writes in place) and coh = 2 b(h') . x - x . R x: at R x = b its value is b . x and its
+    gradient the definition's, 2 x . db."""
+    K = 512
+    n = clean.shape[1]
+    nan = torch.full((1,), float("nan"), dtype=torch.float64)
+    s32, h32 = clean.detach().to(torch.float32), noisy.detach().to(torch.float32)
+    if n == 0 or not bool(torch.isfinite(s32).all() and torch.isfinite(h32).all()):
+        return nan
+    ns = s32.double().square().sum(1).sqrt().float().clamp(min=1e-6)
+    nh_raw = h32.double().square().sum(1).sqrt().float()
+    nh = nh_raw.clamp(min=1e-6)
+    s = (s32 / ns[:, None]).double()
+    q = (h32 / nh[:, None]).double()
+    d = noisy.to(torch.float64) - noisy.detach().to(torch.float64)
+    if bool(nh_raw < 1e-6):
+        h = q + d / nh.double()
+    else:
+        h = q + (d - q * (q * d).sum(1, keepdim=True)) / nh.double()
+    nfft = 1 << (n + K - 1).bit_length()
+    Sf = torch.fft.rfft(s, n=nfft)
+    r = torch.fft.irfft(Sf.abs().square(), n=nfft)[:, :K].contiguous()
+    b = torch.fft.irfft(Sf.conj() * torch.fft.rfft(h, n=nfft), n=nfft)[:, :K]
+    if load_diag is not None:
+        r[:, 0] += float(load_diag)
+    with torch.no_grad():
+        x, bad = _toeplitz_solve(r, b.detach().contiguous(), ~(r[:, 0] > 0))
+        lag = torch.arange(K)
+        xRx = (x[0] * (r[0][(lag[:, None] - lag[None, :]).abs()] @ x[0])).sum()
+        if bool(bad) or not bool(torch.isfinite((b * x).sum())):
+            return nan
+    coh = 2.0 * (b * x).sum(1) - xRx
     ratio = coh / (1.0 - coh).clamp(min=1e-8)
-    val = (10.0 * torch.log10(ratio.clamp(min=1e-8))).to(torch.float32)
-    return torch.where(bad | ~torch.isfinite(coh), nan, val)
+    return 10.0 * torch.log10(ratio.clamp(min=1e-8))
 
 
 # ----------------------------------------------------------------------------- BSS-eval of mixtures

@@ -116,6 +116,9 @@ SIGNATURES = {
     "fsem_lsd_grad_rate_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _c_i64,
                                                _vp]),
     "fsem_resample_rows_grad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_i32, _c_i32, _vp]),
+    "fsem_bsssdr_state_floats": (_c_i64, [_c_i64, _c_i64]),
+    "fsem_bsssdr_state_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    "fsem_bsssdr_grad_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

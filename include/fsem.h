@@ -805,6 +805,57 @@ int fsem_resample_rows_grad_f32(const float *g_out, int64_t rows, int64_t n_in, 
                                 const int32_t *lengths /* NULL: whole rows */, float *grad_in, int64_t ld_in,
                                 int32_t orig_freq, int32_t new_freq, void *stream);
 
+/* ---------------------------------------------------------------- BSS-eval SDR with gradients
+ * The 512-tap BSS-eval SDR of fsem_bsssdr.h as a function to train against: the scores, and the gradient of
+ * L = sum_b g_sdr[b] SDR_b with respect to the denoised rows at 16 kHz.  (The forward entries live in
+ * libfsem_bsssdr.so, whose entry set is pinned; these joined the core at ABI 11 without a bump, as above.)
+ * Notation of fsem_bsssdr.h: s', h' the float32 quotients as doubles, r, b the correlations, x the solution
+ * of R x = b, coh = b . x, nh the float32 clamped norm of the estimate.  b is linear in h' and R does not
+ * depend on it, so d coh / d h'[u] = 2 y[u] with
+ *   y[u] = sum_{k = 0 .. 511} x[k] s'[u - k],  u in [0, n)   (s' = 0 outside [0, n)),
+ * a causal 512-tap FIR of the clean row by the solved filter; through the normalisation, h' . y = coh, so
+ *   d SDR / d h[u] = D (2 / nh) (y[u] - coh h'[u])      the estimate's norm not clamped
+ *   d SDR / d h[u] = D (2 / nh)  y[u]                   its float32 norm < 1e-6: nh is the constant 1e-6
+ *   D = (10 / ln 10) / (coh (1 - coh))                  no clamp active
+ *   D = (10 / ln 10) / coh                              1 - coh < 1e-8: the denominator is the constant 1e-8
+ *   D = 0                                               coh / max(1 - coh, 1e-8) < 1e-8: the score is the constant -80
+ * and grad[b, u] = g_sdr[b] times that.
+ *  - The float32 quotients are part of the definition: the gradient is taken at them, as the score is; the
+ *    float32 rounding of the norm is treated as smooth (d nh / d h = h / nh).  load_diag changes R only.
+ *  - Clean rows are constants: no gradient with respect to ref.
+ *  - A row whose score is NaN (a singular system, a non-finite sample among its lengths[b] samples) gets a
+ *    gradient row of exact zeros, and so does a row with D = 0 (a silent estimate); no other row is touched.
+ *  - With lengths, grad[b, lengths[b] .. length) is zero and row b's gradient is that of the unpadded row;
+ *    what the memory past lengths[b] holds, NaN included, does not reach the output.  Columns of grad at or
+ *    past `length` (grad_ld > length) are not written.
+ *  - Precision: double throughout (the FIR on the vector FMA pipe, by the forward's own inner loop) up to the
+ *    one rounding of the float32 store: y - coh h' cancels to the order of 1 - coh.
+ *  - No atomics; every output has one owner and one order of its 512 terms.  A row's gradient is bitwise the
+ *    same whatever the batch size, the row's position, `length`, `ld`, `grad_ld`, the alignment and the stream.
+ *
+ *   ref, deg : as fsem_bsssdr_f32 takes them ([batch, length] float32, row stride ld; no sample at or past
+ *              lengths[b] is read by the backward)
+ *   state    : [fsem_bsssdr_state_floats(batch, length)] float32, owned by the caller, 256-byte aligned.  Its
+ *              head is the workspace of fsem_bsssdr_load_diag_f32, laid out as that entry lays it out; its
+ *              tail is one record per row: x [512] float64, coh, and the row's flags (a NaN score; the
+ *              estimate's float32 norm below 1e-6, by the forward's own comparison): 4112 bytes per row.
+ *   fsem_bsssdr_state_f32 : sdr [batch] bitwise that of fsem_bsssdr_load_diag_f32 (the same kernels on the
+ *              state's head); leaves the norms and the records in the state.
+ *   fsem_bsssdr_grad_f32  : reads the state fsem_bsssdr_state_f32 left for the same ref, deg, batch, length,
+ *              ld and lengths (it writes nothing there and may be called again) and writes every element of
+ *              grad[b, 0 .. length) (row b at grad + b grad_ld), rounded to float32 once from double.
+ *   g_sdr    : [batch] float32 device array.
+ * FSEM_EINVAL before any launch for null pointers (lengths may be NULL), batch < 0, length < 1,
+ * length > 2^29, ld < length, grad_ld < length or a load_diag that is not finite (fsem_bsssdr_state_floats
+ * returns 0 for such batch and length).  batch == 0 is FSEM_OK with nothing launched.
+ */
+int64_t fsem_bsssdr_state_floats(int64_t batch, int64_t length);  /* 0 for arguments the entries refuse */
+int fsem_bsssdr_state_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                          const int32_t *lengths, double load_diag, float *sdr, float *state, void *stream);
+int fsem_bsssdr_grad_f32(const float *ref, const float *deg, int64_t batch, int64_t length, int64_t ld,
+                         const int32_t *lengths, const float *g_sdr, const float *state,
+                         float *grad, int64_t grad_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
