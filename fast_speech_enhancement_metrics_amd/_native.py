@@ -119,6 +119,12 @@ SIGNATURES = {
     "fsem_bsssdr_state_floats": (_c_i64, [_c_i64, _c_i64]),
     "fsem_bsssdr_state_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, ctypes.c_double, _vp, _vp, _vp]),
     "fsem_bsssdr_grad_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "fsem_dnsmos_grad_scratch_floats": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "fsem_dnsmos_grad_weights_floats": (_c_i64, []),
+    "fsem_dnsmos_grad_pack_weights_f32": (ctypes.c_int, [_vp, _vp, _c_i64, _vp]),
+    "fsem_dnsmos_grad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64,
+                                            _vp]),
+    "fsem_dnsmos_grad_image_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

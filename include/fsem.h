@@ -856,6 +856,73 @@ int fsem_bsssdr_grad_f32(const float *ref, const float *deg, int64_t batch, int6
                          const int32_t *lengths, const float *g_sdr, const float *state,
                          float *grad, int64_t grad_ld, void *stream);
 
+/* ---------------------------------------------------------------- DNSMOS with gradients
+ * The SIG, BAK and OVRL of fsem_dnsmos.h as functions to train against: the gradient of
+ * L = sum_b sum_k g_scores[b][k] score_k(b) with respect to the 16 kHz rows.  (The forward entries live in
+ * libfsem_dnsmos.so, whose entry set is pinned; these joined the core at ABI 11 without a bump, as above.)
+ * It is the gradient of the forward the scores come from, f16 roundings included: every ReLU, pool and
+ * maximum decision is the one the f16 forward took.  Notation of fsem_dnsmos.h.
+ *
+ * Nothing is kept between the forward call and this one.  The entry recomputes each pass of `pass`
+ * segments (1 ... 16, the caller's choice) with the forward's own kernels, recording in the pass's scratch
+ * re and im of the front end (float32), which of its 2 x 2 inputs each pooled element is, and where conv7's
+ * maxima lie; then the adjoint of the pass runs; pass after pass on the stream.  Per segment:
+ *  - Seed: g_scores[b][k] (c1_k + 2 c2_k r_k) / S_b at raw output k, in double, rounded to float32.
+ *  - Dense layers transposed, float32; a ReLU passes the gradient where its output is > 0.  The maximum
+ *    over positions passes a channel's gradient to the first position (row-major) that attains the
+ *    maximum, and nothing when the maximum is 0.
+ *  - Scale: the 64 values at conv7's output are multiplied by the power of two that puts the largest
+ *    magnitude into [8, 16), so that the f16 gradients below stay clear of f16's subnormal range whatever
+ *    the seed's size; the inverse is multiplied back exactly where the image gradient is formed.  A
+ *    segment whose 64 values are all zero (a zero seed) or not all finite is skipped: it adds nothing.
+ *  - Data gradients of conv7 ... conv2 on v_mfma_f32_16x16x32_f16: the forward's implicit GEMM with C_in
+ *    and C_out exchanged, weights rounded to f16 from the same float32 tensors, ordered
+ *    [2 - ky, 2 - kx][C_in][C_out]; float32 accumulation; the gradient of each layer's input is stored as
+ *    f16.  A pooled layer passes the gradient of a pooled element to its winner (the first of the 2 x 2
+ *    in row-major order that attains the maximum, taken on the float32 values) where the pooled f16
+ *    activation is > 0; the row and column that pooling's floor dropped get 0.  conv2 and conv3 pass the
+ *    gradient where the stored f16 activation is > 0.
+ *  - conv2's data gradient (128 channels) is not stored: conv1's pre-activation is recomputed from the
+ *    image (the forward's nine FMAs) for the mask z > 0, and the pixel's 128 channels are contracted with
+ *    conv1's float32 weights into the image gradient [900][161], float32.
+ *  - Front end in double: g_p = g_img / (p ln 10) where the float32 power p > 1e-12, else 0;
+ *    g_re = 2 re g_p, g_im = 2 im g_p; a frame sample is the sum over the bins in ascending order (re's
+ *    term, then im's); the two frames that cover a segment sample are added, the earlier first.
+ *  - Rows: segment s, sample t belongs to row sample (16000 s + t) mod n; a sample of a short row collects
+ *    every wrap, in ascending t, in double; the segments are added in ascending order onto the float32
+ *    gradient, one rounding per segment.
+ * A row flagged non-finite by the forward's rule (its scores are NaN), a row of no samples and a row whose
+ * g_scores are zero get a gradient row of exact zeros; no other row is touched by them.  grad[b, n_b ..
+ * length) is zero; samples at or past n_b are never read; columns of grad at or past `length` are not written.
+ * No float atomics; every sum has one order.  A row's gradient is bitwise the same whatever `pass`, the
+ * batch size, the row's position, `length`, `ld`, `ld_grad`, the alignment and the stream.
+ *
+ *   weights  : the blob of fsem_dnsmos_grad_pack_weights_f32 (fsem_dnsmos_grad_weights_floats() floats,
+ *              256-byte aligned): the forward's blob, the two STFT matrices in the checkpoint's layout and
+ *              the flipped f16 convolution weights, from the same 22 tensors (a HOST array of 22 device
+ *              pointers in state-dict order, as fsem_dnsmos_pack_weights_f32 takes them).
+ *   scratch  : [fsem_dnsmos_grad_scratch_floats(batch, length, pass)] float32, 256-byte aligned, owned by
+ *              the caller; about 92 MB per segment of a pass and 4 bytes per row.
+ *   g_scores : [batch][3] float32 device array.
+ *   grad     : [batch, length] float32 (row stride ld_grad), every element of [b, 0 .. length) written.
+ *   raw      : NULL or [S_total][3]: the raw outputs the entry recomputed, bitwise fsem_dnsmos_raw_f32's.
+ *   fsem_dnsmos_grad_image_f32 : the stage entry, the counterpart of fsem_dnsmos_features_f32: g_image
+ *              [S_total][900][161] float32, the gradient with respect to each segment's log-power image
+ *              (zeros for a skipped segment), and nothing after it.
+ * FSEM_EINVAL before any launch for null pointers (lengths and raw may be NULL), batch < 1, length < 1,
+ * ld < length, ld_grad < length, length > 2^29 or pass outside 1 ... 16 (the scratch query returns 0 for
+ * those); FSEM_EWORKSPACE from the pack entry for a blob that is too small.
+ */
+int64_t fsem_dnsmos_grad_scratch_floats(int64_t batch, int64_t length, int64_t pass);
+int64_t fsem_dnsmos_grad_weights_floats(void);
+int fsem_dnsmos_grad_pack_weights_f32(const float *const *tensors, float *blob, int64_t blob_floats, void *stream);
+int fsem_dnsmos_grad_f32(const float *deg, int64_t batch, int64_t length, int64_t ld, const int32_t *lengths,
+                         const float *weights, const float *g_scores, float *grad, int64_t ld_grad,
+                         float *raw /* or NULL */, float *scratch, int64_t pass, void *stream);
+int fsem_dnsmos_grad_image_f32(const float *deg, int64_t batch, int64_t length, int64_t ld, const int32_t *lengths,
+                               const float *weights, const float *g_scores, float *g_image, float *scratch,
+                               int64_t pass, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
