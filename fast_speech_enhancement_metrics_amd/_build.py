@@ -21,7 +21,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 STAMP_LIB = os.path.join(LIBDIR, "libfsem_stamps.so")  # diagnostic build (tools/stamps.py)
 SOURCES = ["pesq.hip", "pesq_back.hip", "pesq_grad.hip", "stoi.hip", "stoi_grad.hip", "resample.hip", "align.hip", "sdr.hip",
-           "spectral.hip", "srmr.hip", "bsseval.hip", "pitsdr.hip", "lsd_grad.hip", "bsssdr_grad.hip", "dnsmos_grad.hip", "runtime.hip"]
+           "spectral.hip", "srmr.hip", "bsseval.hip", "pitsdr.hip", "lsd_grad.hip", "bsssdr_grad.hip", "dnsmos_grad.hip", "srmr_grad.hip", "runtime.hip"]
 # per-source code-generation flags: the STOI kernels and the resamplers are scheduled for ILP
 # (gfx950's max-ilp machine scheduler: joint call 7.167 vs 7.198 ms, profiles/r4_sc/; config 5
 # 224.0k vs 221.3k utt/s, profiles/r4_fl/; bitwise equal); the PESQ front end keeps the
@@ -39,7 +39,7 @@ _ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 SOURCE_FLAGS = {"pesq.hip": ["-fno-slp-vectorize"], "stoi.hip": _ILP, "resample.hip": _ILP}
 HEADERS = ["fsem_bsssdr_kernels.h", "fsem_build_marker.h", "fsem_common.h", "fsem_complex.h", "fsem_corr512.h", "fsem_dnsmos_kernels.h", "fsem_fft.h",
            "fsem_internal.h", "fsem_lpc.h", "fsem_lsd_kernels.h", "fsem_pesq.h", "fsem_resample.h", "fsem_sdr_rules.h", "fsem_select.h",
-           "fsem_speech_frames.h", "fsem_stoi.h", "fsem_tables.inc", "fsem_vad.h"]
+           "fsem_speech_frames.h", "fsem_srmr_kernels.h", "fsem_stoi.h", "fsem_tables.inc", "fsem_vad.h"]
 HEADER_ABI = os.path.join(PKG, "..", "include", "fsem.h")
 COMPOSITE_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_composite.h")
 LSD_HEADER_ABI = os.path.join(PKG, "..", "include", "fsem_lsd.h")
@@ -64,7 +64,8 @@ class Library(NamedTuple):
 # stoi_grad.hip, fsem_pesq_state_* / fsem_pesq_grad_* in pesq_grad.hip, fsem_lsd_grad_* in lsd_grad.hip,
 # which compiles its own copy of the forward's scale kernels from fsem_lsd_kernels.h, and
 # fsem_bsssdr_state_* / fsem_bsssdr_grad_* in bsssdr_grad.hip, likewise from fsem_bsssdr_kernels.h, and
-# fsem_dnsmos_grad_* in dnsmos_grad.hip, from fsem_dnsmos_kernels.h); they
+# fsem_dnsmos_grad_* in dnsmos_grad.hip, from fsem_dnsmos_kernels.h, and fsem_srmrgrad_* in srmr_grad.hip,
+# from fsem_srmr_kernels.h); they
 # use fsem_common.h (the Arena, the launch helpers) and link alone, except Composite's, whose
 # PESQ stage calls into libfsem.so.  A further library is one more entry here, a binding table in
 # _native, its header and its source.

@@ -1364,18 +1364,27 @@ def srmr_energies(x: np.ndarray, sample_rate: int) -> np.ndarray:
     return A
 
 
-def srmr_score(A: np.ndarray, sample_rate: int) -> np.ndarray:
-    """SRMR of [B, 23, 8] energies: the 90 % bandwidth rule and the ratio."""
+def srmr_bands(A: np.ndarray, sample_rate: int) -> np.ndarray:
+    """K* of [B, 23, 8] energies: the 90 % bandwidth rule, [B] ints."""
     _, _, erb, _, _, L = _srmr_filters(sample_rate)
-    out = np.full(A.shape[0], np.nan)
+    out = np.empty(A.shape[0], dtype=np.int64)
     for b in range(A.shape[0]):
         ac = A[b].sum(1)
         with np.errstate(invalid="ignore", divide="ignore"):
             cum = np.cumsum(100 * ac[::-1] / ac.sum())
             over = np.nonzero(cum > 90)[0]
             bw = erb[SRMR_CHANNELS - 1 - over[0]] if len(over) else erb[0]
-            K = 8 if bw > L[7] else 7 if bw > L[6] else 6 if bw > L[5] else 5
-            out[b] = A[b, :, :4].sum() / A[b, :, 4:K].sum()
+            out[b] = 8 if bw > L[7] else 7 if bw > L[6] else 6 if bw > L[5] else 5
+    return out
+
+
+def srmr_score(A: np.ndarray, sample_rate: int) -> np.ndarray:
+    """SRMR of [B, 23, 8] energies: the 90 % bandwidth rule and the ratio."""
+    K = srmr_bands(A, sample_rate)
+    out = np.full(A.shape[0], np.nan)
+    for b in range(A.shape[0]):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[b] = A[b, :, :4].sum() / A[b, :, 4:K[b]].sum()
     return out
 
 
@@ -1395,6 +1404,85 @@ def srmr(rows: torch.Tensor, sample_rate: int = 16000, return_energies: bool = F
         s[~np.isfinite(x).all(1)] = np.nan
         score, A = torch.from_numpy(s), torch.from_numpy(a)
     return (score, A) if return_energies else score
+
+
+def srmr_gradient(x: np.ndarray, sample_rate: int, A: np.ndarray, g: np.ndarray) -> np.ndarray:
+    """d (sum_b g[b] SRMR_b) / dx of [B, n] float64 rows with at least one frame, given their energies A: the
+    closed form of include/fsem.h "SRMR with gradients", K* taken as a constant.  Every adjoint recurrence
+    is lfilter on the reversed row.  Rows whose score is not finite get zeros."""
+    wi, wl = srmr_geometry(sample_rate)
+    B, n = x.shape
+    F = (n - wl) // wi + 1
+    nend = (F - 1) * wi + wl
+    p, gain, _, mb, ma, _ = _srmr_filters(sample_rate)
+    w2 = np.square(0.54 - 0.46 * np.cos(2 * np.pi * np.arange(wl) / wl))
+    V = np.zeros(nend)
+    for f in range(F):
+        V[f * wi:f * wi + wl] += w2
+    K = srmr_bands(A, sample_rate)
+    c = np.zeros((B, SRMR_MODS))
+    for b in range(B):
+        N, D = A[b, :, :4].sum(), A[b, :, 4:K[b]].sum()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            if np.isfinite(np.float32(N / D)):
+                c[b, :4] = g[b] / D
+                c[b, 4:K[b]] = -g[b] * N / (D * D)
+    dx = np.zeros((B, n))
+    if not c.any():
+        return dx
+    for i in range(SRMR_CHANNELS):
+        taps = np.array([0, p[i], 4 * p[i] ** 2, p[i] ** 3]) / gain[i]
+        y = lfilter(taps, [1.0], x.astype(np.complex128), axis=-1)
+        for _ in range(4):
+            y = lfilter([1.0], [1.0, -p[i]], y, axis=-1)
+        e = np.abs(y)
+        de = np.zeros((B, nend))
+        for k in range(SRMR_MODS):
+            if not c[:, k].any():
+                continue
+            m = lfilter(mb[k], ma[k], e, axis=-1)[:, :nend]
+            q = (2.0 * c[:, k, None] / F) * m * V
+            # r[t] = q[t] - a1 r[t + 1] - a2 r[t + 2], then b0 (r[t] - r[t + 2]): the filter itself, reversed
+            de += lfilter(mb[k], ma[k], q[:, ::-1], axis=-1)[:, ::-1]
+        a = np.zeros((B, n), dtype=np.complex128)
+        live = e[:, :nend] > 0
+        a[:, :nend] = np.where(live, de * y[:, :nend] / np.where(live, e[:, :nend], 1.0), 0.0)  # |y| = 0: 0
+        a = a[:, ::-1]
+        for _ in range(4):
+            a = lfilter([1.0], [1.0, -np.conj(p[i])], a, axis=-1)
+        dx += np.real(lfilter(np.conj(taps), [1.0], a, axis=-1))[:, ::-1]
+    return dx
+
+
+class _Srmr64(torch.autograd.Function):
+    """SRMR [B] float64 of [B, n] float64 rows; the backward is srmr_gradient on the saved rows and energies."""
+
+    @staticmethod
+    def forward(ctx, rows, sample_rate):
+        score, A = srmr(rows, sample_rate, return_energies=True)
+        ctx.rows, ctx.A, ctx.sample_rate = rows.detach(), A, sample_rate
+        return score
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        rows, sr = ctx.rows, ctx.sample_rate
+        B, n = rows.shape
+        grad = torch.zeros(B, n, dtype=torch.float64)
+        x = rows.to(torch.float64).numpy()
+        ok = np.isfinite(x).all(1) if n else np.zeros(B, dtype=bool)
+        if n >= srmr_geometry(sr)[1] and ok.any():
+            with np.errstate(invalid="ignore", over="ignore"):
+                dx = srmr_gradient(x[ok], sr, ctx.A.numpy()[ok], g.to(torch.float64).numpy()[ok])
+            grad[torch.from_numpy(ok)] = torch.from_numpy(np.ascontiguousarray(dx))
+        return grad, None
+
+
+def srmr64(rows: torch.Tensor, sample_rate: int = 16000) -> torch.Tensor:
+    """SRMR [B] float64 of [B, n] float64 host rows, as ``srmr``, carrying the gradient with respect to the
+    rows (include/fsem.h "SRMR with gradients"): an autograd function of its own around the closed form.
+    A row without a frame, with a non-finite sample or with a non-finite score gets a zero gradient row."""
+    return _Srmr64.apply(rows.to(torch.float64), int(sample_rate))
 
 
 # ----------------------------------------------------------------------------- DNSMOS

@@ -125,6 +125,9 @@ SIGNATURES = {
     "fsem_dnsmos_grad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i64,
                                             _vp]),
     "fsem_dnsmos_grad_image_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "fsem_srmrgrad_pass_rows": (_c_i64, [_c_i64]),
+    "fsem_srmrgrad_scratch_bytes": (_c_i64, [_c_i64, _c_i64]),
+    "fsem_srmrgrad_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _vp, _vp]),
 }
 # every symbol include/fsem_composite.h declares (libfsem_composite.so)
 COMPOSITE_SIGNATURES = {

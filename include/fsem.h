@@ -923,6 +923,51 @@ int fsem_dnsmos_grad_image_f32(const float *deg, int64_t batch, int64_t length, 
                                const float *weights, const float *g_scores, float *g_image, float *scratch,
                                int64_t pass, void *stream);
 
+/* ---------------------------------------------------------------- SRMR with gradients
+ * SRMR ("SRMR" above, its notation) as a function to train against: the gradient of L = sum_b gout[b] SRMR_b
+ * with respect to the rows.  (Joined the core at ABI 11 without a bump, as above.  The entries are named
+ * fsem_srmrgrad_*: the set of names that begin with fsem_srmr_ is the forward's and is pinned.)  K* is a decision and is
+ * taken as a constant.  Per row, with G = gout[b], N and D the ratio's numerator and denominator, per channel
+ * i with pole p and gain g (v, the four stages s_j with y = s_4, e = |y|, m_k as in the forward):
+ *  1. c_k = G / D for k < 4; -G N / D^2 for 4 <= k < K*; 0 for k >= K*.  The same c_k for every channel.
+ *  2. q_ik[t] = (2 c_k / F) m_ik[t] V[t] for t < nend = (F - 1) wi + wl, and 0 from nend on.
+ *  3. The adjoint biquad runs backwards in time: r_ik[t] = q_ik[t] - a1_k r_ik[t + 1] - a2_k r_ik[t + 2], r = 0
+ *     from nend on; de_i[t] = sum_k b0_k (r_ik[t] - r_ik[t + 2]).
+ *  4. a0_i[t] = de_i[t] y_i[t] / |y_i[t]|, exactly 0 where |y_i[t]| = 0 (the subgradient 0).
+ *  5. Four adjoint stages backwards in time with the conjugate pole: a^j[t] = conj(p) a^j[t + 1] + a^(j-1)[t].
+ *  6. dx[t] = sum_i Re(conj(p) a4_i[t + 1] + 4 conj(p)^2 a4_i[t + 2] + conj(p)^3 a4_i[t + 3]) / g_i.
+ * dx[t] is exactly 0 for t >= nend - 1.  SRMR does not depend on the row's scale: sum_t dx[t] x[t] = 0 up to
+ * rounding, and the gradient scales with 1 / gain.
+ *
+ * Row conventions.  A row with F = 0, a row with a non-finite sample among its first n, a row whose score is
+ * not finite (a digitally silent row) and a row whose gout is 0 get a gradient row of exact zeros; no other row
+ * is touched by them.  grad[b, t] is written as zero for t >= nend - 1 and for t >= n_b; samples at or past
+ * n_b are never read; columns of grad at or past `length` are not written.
+ *
+ * Precision and order.  Nothing of the forward is kept but `energies`.  The entry walks a row's 4096-sample
+ * tiles twice per channel: first to last, storing the filter state that enters each tile (184 bytes per row,
+ * channel and tile); then last to first, recomputing the tile's y and envelope from that state with the
+ * forward's own code and running steps 2 - 6 on it, with the adjoint states carried to the tile before.  The
+ * modulation recurrences, their adjoints and de are double; the gammatone, y / |y| and the adjoint stages are
+ * float32 complex, with the forward's constants.  The sum over k is ((0 + 1) + (2 + 3) + (4 + 5)) + (6 + 7);
+ * each channel's dx goes to a float32 plane in scratch and the 23 planes are added in channel order in double,
+ * rounded once.  Rows are processed in passes of fsem_srmrgrad_pass_rows(length) rows (at most 2 GiB of planes
+ * and checkpoints).  No float atomics; a row's gradient is bitwise the same whatever the pass it falls in, the
+ * batch size, the row's position, `length`, `ld` and the stream.
+ *   deg, lengths, sample_rate : as fsem_srmr_f32 took them
+ *   energies : [batch][23][8] float64, as fsem_srmr_f32 wrote them for these rows
+ *   gout     : [batch] float32 device array, the incoming gradients
+ *   scratch  : fsem_srmrgrad_scratch_bytes(batch, length) bytes, 256-byte aligned, owned by the caller
+ *   grad     : [batch, length] float32 with the rows' own stride ld; every element of [b, 0 .. length) written
+ * FSEM_EINVAL before any launch for null pointers (lengths may be NULL), batch < 1, length < 1, ld < length or
+ * length > 2^29 (the queries return 0 for those); FSEM_ERATE for another sample rate.
+ */
+int64_t fsem_srmrgrad_pass_rows(int64_t length);                    /* rows per pass, from length alone */
+int64_t fsem_srmrgrad_scratch_bytes(int64_t batch, int64_t length); /* 0 for arguments the entry refuses */
+int fsem_srmrgrad_f32(const float *deg, int64_t batch, int64_t length, int64_t ld, const int32_t *lengths,
+                      int32_t sample_rate, const double *energies, const float *gout, void *scratch, float *grad,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
